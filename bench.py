@@ -24,7 +24,16 @@ disorder replicas per rank (weak scaling), no collective in the data path;
 torch.distributed (RCCL) only for the barrier, the max-time reduction and the
 observable gather.
 
+A plain run sets up, thermalises, warms up, times --steps and prints the
+result line.  --full adds what takes runs of its own after the timed region:
+the per-kernel replay with HIP events (roofline, cr_*, assembly), the C1 side
+line and the CPU baseline (--no-timing / --no-c1 / --no-cpu-baseline drop one
+of them).  --dump-outputs DIR writes the chain state and the Metropolis
+results the timed sweeps end with as DIR/<name>.npy; the inputs are seeded, so
+two builds run with the same arguments compare output for output.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+                       [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -186,10 +195,15 @@ def parse(argv=None):
     ap.add_argument("--Nt", type=int, default=10, help="Nt_therm_init (src/Simulation.jl:38)")
     ap.add_argument("--therm", type=int, default=100,
                     help="thermalisation sweeps with the adaptive-Nt rule (src/Simulation.jl:104-130)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also run the per-kernel replay (roofline, assembly), the C1 "
+                         "side line and the CPU baseline; a plain run times --steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed sweeps returned (Delta, pi, accepted, dH) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=0, help="oracle leapfrog steps for the CPU leg (0 = auto)")
-    ap.add_argument("--no-c1", action="store_true", help="skip the C1 (L=8, beta=4) side line")
-    ap.add_argument("--no-timing", action="store_true", help="disable per-kernel HIP events")
+    ap.add_argument("--no-c1", action="store_true", help="with --full: skip the C1 (L=8, beta=4) side line")
+    ap.add_argument("--no-timing", action="store_true", help="with --full: skip the per-kernel HIP-event replay")
     ap.add_argument("--algo", choices=["auto", "dense", "cr"], default="auto",
                     help="factorisation (include/dwhmc.h DWH_ALGO_*); auto = cyclic reduction when 2L <= 128")
     a = ap.parse_args(argv)
@@ -250,6 +264,20 @@ def thermalise(m, ctx, p, replica, nchains, n_therm, Nt0):
             accs.append(float(acc[j].mean()))
             ad.record(i + j + 1, accs[-1] >= 0.5)
     return ad.Nt, float(np.mean(accs[-20:]))
+
+
+def dump_outputs(out_dir, ctx, acc, dH, rank, world):
+    """What a caller of the timed path holds after its last sweep, as float64
+    DIR/<name>.npy: the chain state (Delta, pi: (chains, N, 2, 2) with the
+    last axis (re, im)) and the Metropolis results of the timed sweeps
+    (accepted, dH: (sweeps, chains)).  Ranks above 0 add a .rank<r> suffix."""
+    os.makedirs(out_dir, exist_ok=True)
+    Delta, pi = ctx.get_state()
+    sfx = f".rank{rank}" if world > 1 and rank else ""
+    for name, arr in (("Delta", Delta), ("pi", pi)):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.stack([arr.real, arr.imag], axis=-1))
+    np.save(os.path.join(out_dir, f"accepted{sfx}.npy"), acc.astype(np.float64))
+    np.save(os.path.join(out_dir, f"dH{sfx}.npy"), np.asarray(dH, dtype=np.float64))
 
 
 def cpu_model() -> str:
@@ -452,10 +480,12 @@ def main(argv=None):
                         for x in torch.stack(gl).cpu().numpy()]
 
     acc, dH = ctx.sweep_results(w_sw, n_draws(timed))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, ctx, acc, dH, rank, world)
     info = ctx.info
     kern = {}
     replay_steps = 0
-    if not a.no_timing:
+    if a.full and not a.no_timing:
         # Per-kernel HIP events (on the context's stream) in an instrumented
         # replay of the timed schedule's first <= 2 Nt steps right after the
         # timed region: each event record is a barrier packet that costs ~20 %
@@ -637,9 +667,9 @@ def main(argv=None):
                                                        "committed profile, not this run)" if pr_us else None),
                                    "what": f"{ASSEMBLY_REPS} back-to-back warm launches (dwh_bench_assembly) "
                                            "after the timed region"}
-        if world == 1 and not a.no_c1 and a.L != PRESETS["C1"]["L"]:
+        if a.full and world == 1 and not a.no_c1 and a.L != PRESETS["C1"]["L"]:
             rec["c1"] = c1_line(m, local)
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             steps_all = a.cpu_steps or (1 if a.L >= 48 else 3 if a.L >= 32 else 20)
             steps_one = 0 if a.L >= 48 else 1 if a.L >= 32 else 5
             rec["cpu_baseline"] = cpu_baseline(p_args, dis[0], D0[0], steps_all, steps_one)

@@ -13,13 +13,13 @@ if [ "${2:-}" != "skip-tests" ]; then
   tail -3 "$O/tests.log"
 fi
 for tab in budget strict; do
-  DWHMC_POLE_TABLE=$tab timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 \
+  DWHMC_POLE_TABLE=$tab timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 \
     > "$O/bench_C3_$tab.json" 2> "$O/bench_C3_$tab.err" || { tail -20 "$O/bench_C3_$tab.err"; exit 1; }
-  DWHMC_POLE_TABLE=$tab timeout -k 10 300 python -u bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
+  DWHMC_POLE_TABLE=$tab timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
     > "$O/bench_C3_200_$tab.json" 2> "$O/bench_C3_200_$tab.err" || { tail -20 "$O/bench_C3_200_$tab.err"; exit 1; }
-  DWHMC_POLE_TABLE=$tab timeout -k 10 300 python -u bench.py --config C2 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
+  DWHMC_POLE_TABLE=$tab timeout -k 10 300 python -u bench.py --full --config C2 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
     > "$O/bench_C2_$tab.json" 2> "$O/bench_C2_$tab.err" || { tail -20 "$O/bench_C2_$tab.err"; exit 1; }
-  DWHMC_POLE_TABLE=$tab timeout -k 10 300 python -u bench.py --config C5 --steps 40 --warmup 8 --no-cpu-baseline --no-c1 \
+  DWHMC_POLE_TABLE=$tab timeout -k 10 300 python -u bench.py --full --config C5 --steps 40 --warmup 8 --no-cpu-baseline --no-c1 \
     > "$O/bench_C5_$tab.json" 2> "$O/bench_C5_$tab.err" || { tail -20 "$O/bench_C5_$tab.err"; exit 1; }
 done
 python - "$O" <<'PY'

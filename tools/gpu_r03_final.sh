@@ -14,16 +14,16 @@ if [ "${2:-}" != "skip-tests" ]; then
     --timeout 450 --timeout-method thread > "$O/tests.log" 2>&1 || { tail -40 "$O/tests.log"; exit 1; }
   tail -3 "$O/tests.log"
 fi
-timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
+timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
   || { tail -20 "$O/bench_driver.err"; exit 1; }
-timeout -k 10 300 python -u bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
+timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
   > "$O/bench_C3_200.json" 2> "$O/bench_C3_200.err" || exit 1
 bash tools/profile_round.sh "$TAG" r03 || exit 1
 python3 tools/trace_step.py "$R/gpurun_out/prof_$TAG/stats/run_kernel_trace.csv" > "$O/step.txt" || exit 1
 rm -f "$R/gpurun_out/prof_$TAG/stats/run_kernel_trace.csv"
-timeout -k 10 300 python -u bench.py --config C2 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
+timeout -k 10 300 python -u bench.py --full --config C2 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
   > "$O/bench_C2.json" 2> "$O/bench_C2.err" || exit 1
-timeout -k 10 300 python -u bench.py --config C5 --steps 40 --warmup 8 --no-cpu-baseline --no-c1 \
+timeout -k 10 300 python -u bench.py --full --config C5 --steps 40 --warmup 8 --no-cpu-baseline --no-c1 \
   > "$O/bench_C5.json" 2> "$O/bench_C5.err" || exit 1
 timeout -k 10 200 python -u tests/bench_transport.py --steps 3 --snapshots 4,8,16 > "$O/transport.json" 2> "$O/transport.err" || exit 1
 python - "$O" <<'PY'

@@ -34,13 +34,13 @@ for step in "$@"; do
         --extra-eta-mults 1.25 --out "$O/tscan" > "$O/tscan.log" 2>&1 || { tail -20 "$O/tscan.log"; exit 1; }
       tail -5 "$O/tscan.log" ;;
     bench)
-      timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
+      timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
         || { tail -20 "$O/bench_driver.err"; exit 1; }
-      timeout -k 10 300 python -u bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
+      timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
         > "$O/bench_C3_200.json" 2> "$O/bench_C3_200.err" || exit 1
-      timeout -k 10 300 python -u bench.py --config C2 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
+      timeout -k 10 300 python -u bench.py --full --config C2 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
         > "$O/bench_C2.json" 2> "$O/bench_C2.err" || exit 1
-      timeout -k 10 300 python -u bench.py --config C5 --steps 40 --warmup 8 --no-cpu-baseline --no-c1 \
+      timeout -k 10 300 python -u bench.py --full --config C5 --steps 40 --warmup 8 --no-cpu-baseline --no-c1 \
         > "$O/bench_C5.json" 2> "$O/bench_C5.err" || exit 1
       python - "$O" <<'PY'
 import json, sys, glob, os
@@ -59,7 +59,7 @@ PY
       rm -f "$R/gpurun_out/prof_$TAG/stats/run_kernel_trace.csv" ;;
     profc2)
       (export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/profc2" -o run -- \
-        python3 bench.py --config ${PROF_CFG:-C2} --steps ${PROF_STEPS:-200} --warmup 20 --no-cpu-baseline --no-c1 > "$O/profc2.json" 2> "$O/profc2.err") \
+        python3 bench.py --full --config ${PROF_CFG:-C2} --steps ${PROF_STEPS:-200} --warmup 20 --no-cpu-baseline --no-c1 > "$O/profc2.json" 2> "$O/profc2.err") \
         || { tail -20 "$O/profc2.err"; exit 1; }
       python3 tools/trace_step.py "$O/profc2/run_kernel_trace.csv" > "$O/step_c2.txt" || exit 1
       rm -f "$O/profc2/run_kernel_trace.csv"; tail -25 "$O/step_c2.txt" ;;
@@ -74,7 +74,7 @@ PY
       rm -f "$O/mfma_f64_peak" ;;
     c2rows)
       for r in 1 2 1 2; do
-        DWHMC_CR_ROWS=$r timeout -k 10 300 python -u bench.py --config C2 --steps 200 --warmup 20 --no-cpu-baseline \
+        DWHMC_CR_ROWS=$r timeout -k 10 300 python -u bench.py --full --config C2 --steps 200 --warmup 20 --no-cpu-baseline \
           --no-c1 > "$O/bench_C2_rows$r.json" 2> "$O/bench_C2_rows$r.err" || exit 1
         python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1], round(d['value'],1), d['config']['poles'], d.get('cr_inv'), d.get('cr_inv_side'))" "$O/bench_C2_rows$r.json"
       done ;;
@@ -96,7 +96,7 @@ PY
         --timeout 300 --timeout-method thread > "$O/parity.log" 2>&1 || { tail -40 "$O/parity.log"; exit 1; }
       tail -3 "$O/parity.log" ;;
     driver)
-      timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
+      timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
         || { tail -20 "$O/bench_driver.err"; exit 1; }
       tail -c 1500 "$O/bench_driver.json" ;;
     transab)   # single-measurement latency: every pass writing (defer from 4 matrices) vs deferred from 1

@@ -39,17 +39,17 @@ for step in "$@"; do
         > "$O/tests.log" 2>&1 || { tail -40 "$O/tests.log"; exit 1; }
       tail -3 "$O/tests.log" ;;
     driver)
-      timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
+      timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
         || { tail -20 "$O/bench_driver.err"; exit 1; }
       summ "$O/bench_driver.json" ;;
     bench)
-      timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
+      timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
         || { tail -20 "$O/bench_driver.err"; exit 1; }
-      timeout -k 10 300 python -u bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
+      timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
         > "$O/bench_C3_200.json" 2> "$O/bench_C3_200.err" || exit 1
-      timeout -k 10 300 python -u bench.py --config C2 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
+      timeout -k 10 300 python -u bench.py --full --config C2 --steps 200 --warmup 20 --no-cpu-baseline --no-c1 \
         > "$O/bench_C2.json" 2> "$O/bench_C2.err" || exit 1
-      timeout -k 10 300 python -u bench.py --config C5 --steps 40 --warmup 8 --no-cpu-baseline --no-c1 \
+      timeout -k 10 300 python -u bench.py --full --config C5 --steps 40 --warmup 8 --no-cpu-baseline --no-c1 \
         > "$O/bench_C5.json" 2> "$O/bench_C5.err" || exit 1
       summ "$O"/bench_*.json ;;
     sq3)
@@ -69,7 +69,7 @@ for step in "$@"; do
       rm -f "$R/gpurun_out/prof_$TAG/stats/run_kernel_trace.csv" ;;
     profc2)
       (export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/profc2" -o run -- \
-        python3 bench.py --config ${PROF_CFG:-C2} --steps ${PROF_STEPS:-200} --warmup 20 --no-cpu-baseline --no-c1 > "$O/profc2.json" 2> "$O/profc2.err") \
+        python3 bench.py --full --config ${PROF_CFG:-C2} --steps ${PROF_STEPS:-200} --warmup 20 --no-cpu-baseline --no-c1 > "$O/profc2.json" 2> "$O/profc2.err") \
         || { tail -20 "$O/profc2.err"; exit 1; }
       python3 tools/trace_step.py "$O/profc2/run_kernel_trace.csv" > "$O/step_c2.txt" || exit 1
       rm -f "$O/profc2/run_kernel_trace.csv"; tail -25 "$O/step_c2.txt" ;;

@@ -8,7 +8,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 timeout -k 10 600 python -u -m pytest "$R/tests" -m gpu -x -q --timeout 120 --timeout-method thread \
   > "$O/tests.log" 2>&1
-DWHMC_CR_PLAN_DUMP=1 timeout -k 10 200 python3 "$R/bench.py" --no-cpu-baseline "$@" > "$O/bench.json" 2> "$O/plan.txt"
+DWHMC_CR_PLAN_DUMP=1 timeout -k 10 200 python3 "$R/bench.py" --full --no-cpu-baseline "$@" > "$O/bench.json" 2> "$O/plan.txt"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- \
   python3 "$R/bench.py" --steps 20 --warmup 10 --no-cpu-baseline --no-timing "$@" > "$O/prof_bench.json" 2> "$O/prof.err"

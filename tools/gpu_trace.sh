@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:?tag}; CFG=${2:?config}; shift 2
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
-DWHMC_CR_PLAN_DUMP=1 timeout -k 10 200 python3 "$R/bench.py" --config "$CFG" --steps 50 --warmup 10 --no-cpu-baseline --no-c1 "$@" \
+DWHMC_CR_PLAN_DUMP=1 timeout -k 10 200 python3 "$R/bench.py" --full --config "$CFG" --steps 50 --warmup 10 --no-cpu-baseline --no-c1 "$@" \
   > "$O/bench_$CFG.json" 2> "$O/plan_$CFG.txt" || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$CFG" -o run -- \

@@ -20,7 +20,7 @@ run_group() {   # name counters...
   echo "pass $name: ${keep[*]}"
   [ ${#keep[@]} -gt 0 ] || return 0
   timeout -s KILL 90 rocprofv3 --pmc "${keep[@]}" --output-format csv -d "$O/sq3_$name" -o run -- \
-    python3 "$R/bench.py" $ARGS > "$O/sq3_$name.log" 2>&1
+    python3 "$R/bench.py" --full $ARGS > "$O/sq3_$name.log" 2>&1
 }
 run_group A SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS || exit 1
 run_group B SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC || exit 1
