@@ -14,19 +14,18 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libdwhmc.so")
-SOURCES = [os.path.join(CSRC, "dwhmc_kernels.hip"), os.path.join(CSRC, "dwhmc_cr.hip"), os.path.join(CSRC, "dwhmc_cr_sparse.hip"),
-           os.path.join(CSRC, "dwhmc_eig.hip"), os.path.join(CSRC, "dwhmc_gemm.hip"),
-           os.path.join(CSRC, "dwhmc_transport.hip"), os.path.join(CSRC, "dwhmc_qeig.hip"),
-           os.path.join(CSRC, "dwhmc_api.cpp")]
+# every translation unit and header under csrc/ (a new file is picked up without
+# being listed here, so needs_build() cannot miss it): kernels, then host code
+_CSRC = sorted(os.listdir(CSRC))
+SOURCES = [os.path.join(CSRC, f) for ext in (".hip", ".cpp") for f in _CSRC if f.endswith(ext)]
 # rocSOLVER (zheevd for an order above kEigMaxN, zheev as the re-solve of a
 # non-finite result) is the
 # only vendor library the measurement path can call; every product runs on the
 # library's own MFMA kernel (dwhmc_gemm.hip).  rocBLAS is linked for the
 # rocsolver handle only.
 LIBS = ["-L/opt/rocm/lib", "-lrocsolver", "-lrocblas", "-Wl,-rpath,/opt/rocm/lib"]
-DEPS = SOURCES + [os.path.join(CSRC, "dwhmc_internal.h"), os.path.join(CSRC, "dwhmc_device.h"),
-                  os.path.join(CSRC, "pole_table.inc"), os.path.join(CSRC, "pole_table_eps5e-12.inc"),
-                  os.path.join(ROOT, "include", "dwhmc.h")]
+DEPS = SOURCES + [os.path.join(CSRC, f) for f in _CSRC if f.endswith((".h", ".inc"))] + [
+    os.path.join(ROOT, "include", "dwhmc.h")]
 # gfx950 only: several kernels use more than the 64 KiB of LDS per workgroup
 # earlier CDNA parts allow (k_gemm<complex> 66.5 KiB, k_cr_inv0_96 ~119 KiB),
 # and the tiling is sized for CDNA4's 160 KiB per CU

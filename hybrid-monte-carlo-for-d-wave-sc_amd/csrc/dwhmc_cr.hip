@@ -10,7 +10,7 @@
 // backward pass recovers the block-tridiagonal part of G = (H - i y)^-1,
 // which holds every entry the force (G12 at the pairing bonds), E_f (ln|det|
 // from the block pivots) and Tr ρ_hh (diag G22) need.  The host planner
-// (dwhmc_api.cpp, mirrored by tools/cr_model.py) turns the recursion into
+// (dwhmc_plan.cpp, mirrored by tools/cr_model.py) turns the recursion into
 // stages: block inversions (k_cr_inv) and task lists of block products
 // (k_cr_gemm), all batched over (chain, pole).
 //
@@ -1407,10 +1407,6 @@ __global__ __launch_bounds__(256) void k_cr_fermion_energy(const double2* __rest
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-bool cr_supported_bp(int BP) { return BP == 32 || BP == 64 || BP == 96 || BP == 128; }
-bool cr_supported_side(int BP) { return BP == 64; }
-bool cr_supported_inv0(int BP) { return BP == 64 || BP == 32 || BP == 96; }
-
 void launch_cr_inv0(const CrDims& c, double2* pool, const int* blk, const int* rblk, const int* dst,
                     const int* slot, int n, double* ldpart, const double* ldA, hipStream_t s,
                     const double2* Delta, const int* site4, double cap4, int* flag) {
@@ -1477,84 +1473,6 @@ void launch_cr_inv_side(const CrDims& c, double2* pool, const int* blk, const in
   const dim3 g(n * c.nbatch + side_wg + (sg.Delta != nullptr ? nc : 0));
   hipLaunchKernelGGL(k_cr_inv_side<4>, g, dim3(256), 0, s, pool, c.item, blk, dst, n, c.nbatch, slot, ldpart,
                      c.Ly, side_wg, stasks, nst, maxt32, total, sg, c.N);
-}
-
-// Stage configuration (tile TS, K split).  16 x 16 tiles; the K split by the
-// stage's size (ntiles16 16 x 16 output tiles per batch item x nbatch): a
-// 4-way split (short serial MFMA chains on many waves) for the stages of a
-// single L = 32 chain, whose stages are short and latency bound
-// (profiles/r01_cr_gemm_config_sweep.txt: fastest on every stage there), no
-// split once a stage has enough tiles to fill the chip by itself (batched
-// chains, L = 48: no LDS reduction, one tile per wave;
-// profiles/r03_exp_gemm_ksplit_by_size.txt: from 2048 tiles, C3 -0.9 %,
-// C5 -5 %, 4 chains at L = 32 -3 %; C2's stages stay below it).
-// DWHMC_CR_GEMM=TS:KSPLIT forces one
-// configuration for every stage (A/B runs; tests/test_gpu_parity.py runs
-// every compiled variant).
-CrGemmCfg cr_gemm_config(const CrDims& c, int ntasks, int maxt32, int maxt16, int ntmax, int ntiles16) {
-  (void)ntasks;
-  (void)maxt32;
-  (void)maxt16;
-  (void)ntmax;
-  // read at every context creation (tests switch it between contexts)
-  const CrGemmCfg forced = [] {
-    CrGemmCfg f{0, 1};
-    if (const char* e = std::getenv("DWHMC_CR_GEMM")) {
-      f.ts = std::atoi(e);
-      if (const char* p = std::strchr(e, ':')) f.ksplit = std::atoi(p + 1);
-    }
-    if (f.ksplit != 1 && f.ksplit != 2 && f.ksplit != 4) f.ksplit = 1;
-    if (f.ts == 32 && f.ksplit == 4) f.ksplit = 2;
-    return f;
-  }();
-  const bool ts32_ok = (c.BP / 2) % 32 == 0;   // 32-wide tiles must not straddle A | B
-  if (forced.ts == 16 || (forced.ts == 32 && ts32_ok)) return forced;
-  const int64_t T = (int64_t)ntiles16 * c.nbatch;
-  return CrGemmCfg{16, T >= 2048 ? 1 : 4};
-}
-
-// host twin of xcd_remap (dwhmc_device.h)
-static int xcd_remap_host(int orig, int total) {
-  const int q = total / 8, r = total % 8, xcd = orig % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-}
-
-int cr_gemm_slot_wgs(const CrDims& c, int ntl16, const CrGemmCfg& cfg) {
-  const int tpw = 4 / cfg.ksplit;
-  return (c.nbatch * ntl16 + tpw - 1) / tpw;
-}
-
-// Slot b * TPW + j of the launch = tile (xcd_remap(b, nwg) * TPW + j) of the
-// stage's nbatch x ntl16 tiles (batch item major): the order the round-5
-// kernel derived on the device, so the work distribution over XCDs is kept.
-void cr_gemm_slots(const CrDims& c, const CrTile* tl16, int ntl16, const CrGemmCfg& cfg, CrSlot* out) {
-  const int tpw = 4 / cfg.ksplit, nwg = cr_gemm_slot_wgs(c, ntl16, cfg), HP = c.BP / 2;
-  const int64_t total = (int64_t)c.nbatch * ntl16, BB = (int64_t)HP * c.BP;
-  for (int b = 0; b < nwg; ++b)
-    for (int j = 0; j < tpw; ++j) {
-      CrSlot& sl = out[(size_t)b * tpw + j];
-      sl = CrSlot{};
-      const int64_t gt = (int64_t)xcd_remap_host(b, nwg) * tpw + j;
-      if (gt >= total) {   // padding of the last workgroup
-        sl.out = kCrNone;
-        sl.cin = kCrNone;
-        continue;
-      }
-      const int bi = (int)(gt / ntl16);
-      const CrTile& t = tl16[gt - (int64_t)bi * ntl16];
-      const int r0 = 16 * t.tr, c0 = 16 * t.tc;
-      sl.base = (uint64_t)bi * (uint64_t)c.item;
-      sl.out = (uint32_t)(t.out * BB + (int64_t)r0 * c.BP + c0);
-      sl.cin = t.cin >= 0 ? (uint32_t)(t.cin * BB + (int64_t)r0 * c.BP + c0) : kCrNone;
-      sl.nt = t.nt;
-      for (int h = 0; h < t.nt; ++h) {
-        sl.a[h] = (uint32_t)(t.a[h] * BB + (int64_t)r0 * c.BP);
-        sl.b[h] = (uint32_t)(t.b[h] * BB + c0);
-        const bool q = (t.bq >> h) & 1;
-        if ((c0 < HP) == q) sl.smask |= 1u << h;   // synthesised rows: sgn < 0
-      }
-      sl.rot = (c0 < HP ? c0 + HP : c0 - HP) - c0;
-    }
 }
 
 void launch_cr_gemm(const CrDims& c, double2* pool, const CrTask* tasks, int ntasks, int maxt32,

@@ -367,8 +367,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesB<B
 
 }  // namespace
 
-bool cr_supported_sparse0(int BP) { return BP == 32 || BP == 64 || BP == 96; }
-
 void launch_cr_sp_fwd(const CrDims& c, double2* pool, const CrSpFwd* tasks, int n, const int* trow,
                       const double2* tcv, const int* tcm, const double2* Delta, hipStream_t s) {
   if (n <= 0) return;

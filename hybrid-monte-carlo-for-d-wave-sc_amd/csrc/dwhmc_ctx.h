@@ -1,0 +1,289 @@
+// The C-ABI context (struct dwh_ctx) and the helpers every file that drives
+// the device shares: error returns, device allocation, the event timers, and
+// the few functions that cross between dwhmc_api.cpp (steps, creation, HMC)
+// and dwhmc_measure.cpp (eigensolver driver, transport).  Private to those
+// two files.  Not part of the public ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rocblas/rocblas.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/dwhmc.h"
+#include "dwhmc_internal.h"
+#include "dwhmc_model.h"
+#include "dwhmc_plan.h"
+
+namespace dwh {
+
+enum TimerName {
+  T_GJ_UPDATE = 0, T_GJ_PIVOT, T_ASSEMBLE, T_CONTRACT, T_STEP, T_GJ_EDGE, T_CR_GEMM, T_CR_INV, T_CR_INVSIDE,
+  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_COUNT
+};
+inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assemble", "contract",
+                                                 "step",      "gj_edge",  "cr_gemm",  "cr_inv",
+                                                 "cr_inv_side",
+                                                 "eig_own",   "eig_vendor",   // eigensolves (work: matrices)
+                                                 "cr_sparse"};
+
+enum Algo { ALGO_DENSE = 0, ALGO_CR = 1, ALGO_EIG = 2 };
+
+struct TimingRec {
+  int name;
+  hipEvent_t a, b;
+  double work;
+};
+
+}  // namespace dwh
+
+struct dwh_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  dwh::Dims d{};
+  int64_t Lx = 0, Ly = 0;
+  double t = 0, tp = 0, mu = 0, beta = 0, J = 0, delta_cap = 2.0;
+  // guard: per site (mean |Δ| of its 4 bonds <= delta_cap, checked by the
+  // level-0 inversion launch) or per bond (|Δ_ij| <= delta_cap, the drift kernels)
+  bool site_guard = false;
+  std::vector<int> site4_host;   // per site: the Delta indices of its 4 bonds
+  int* site4 = nullptr;
+  double kappa = 0, Ebound = 0, Cx = 0, err_tanh = 0, hmax = 0;
+  std::vector<double> y, cq;
+  // creation inputs kept for a pole re-selection (reselect_poles)
+  std::vector<int64_t> nn_host, nnn_host;
+  std::vector<double> dis_host;
+  int reselections = 0;
+  int64_t device_bytes = 0;
+  bool factorized = false;
+  std::string err;
+
+  // device buffers
+  double2 *R = nullptr, *S = nullptr;
+  double2* Dv = nullptr;   // pairing values of D per chain (nc x N x kSlots)
+  // Gauss-Jordan panels: column panels CpA[2] (parity), CpB; row panels XR1/XR2; pivots Pb1/Pb2
+  double2 *CpA0 = nullptr, *CpA1 = nullptr, *CpB = nullptr, *XR1 = nullptr, *XR2 = nullptr,
+          *Pb1 = nullptr, *Pb2 = nullptr;
+  double2 *G12nn = nullptr, *diagS = nullptr;
+  double *ldpart = nullptr, *ldstatic = nullptr, *d_y = nullptr, *d_c = nullptr;
+  int *Dcol = nullptr, *Dsrc = nullptr, *hcol = nullptr, *bond_ij = nullptr, *bond_ji = nullptr;
+  double* hval = nullptr;
+  double2 *Delta = nullptr, *Pi = nullptr, *Pair = nullptr, *F = nullptr, *DeltaB = nullptr,
+          *PairB = nullptr;
+  double *Ef = nullptr, *EfB = nullptr, *Trhh = nullptr, *TrhhB = nullptr, *Hold = nullptr,
+         *Hnew = nullptr;
+  int* flag = nullptr;
+  // guard trips inside a batch of throughput sweeps (dwh::SweepHalt): halt[0]
+  // halted, halt[1] sequence number of the tripped sweep in `enq`
+  int* halt = nullptr;
+  struct EnqSweep {
+    int64_t sweep, Nt;
+    double dt, mass;
+  };
+  std::vector<EnqSweep> enq;   // throughput sweeps enqueued since the last settle()
+  // draws / results: single-sweep scratch (s_*) and the throughput path
+  double2* s_noise = nullptr;
+  double* s_uniform = nullptr;
+  uint8_t* s_acc = nullptr;
+  double* s_dH = nullptr;
+  int64_t ndraws = 0;
+  double2* noise = nullptr;
+  double* uniform = nullptr;
+  uint8_t* acc = nullptr;
+  double* dH = nullptr;
+  std::vector<void*> allocations;
+
+  // block cyclic-reduction path (algo == ALGO_CR)
+  int algo = dwh::ALGO_DENSE;
+  dwh::CrDims cr{};
+  dwh::CrPlan plan;
+  double2* bpool = nullptr;   // CR block pool (nbatch x nblk blocks)
+  dwh::CrTask* d_tasks = nullptr;
+  dwh::CrSlot* d_slots = nullptr;
+  dwh::CrSpFwd* d_sp_fwd = nullptr;
+  dwh::CrSpBwd* d_sp_bwd = nullptr;
+  dwh::SpTaskArrays sp_arr;   // the sparse stages' per-task operand arrays
+  int *d_sp_row = nullptr, *d_sp_cm = nullptr;
+  double2* d_sp_cv = nullptr;
+  double* efpart = nullptr;     // per (chain, pole) E_f / Tr G22 partials
+  unsigned* efdone = nullptr;   // per chain: pole blocks done (k_cr_fermion_energy)
+  int *d_inv_blk = nullptr, *d_inv_dst = nullptr, *d_inv_slot = nullptr, *d_inv0_r = nullptr;
+  double* ldA = nullptr;   // static ln|det| of the Δ = 0 level-0 blocks (= 2 ln|det A|) per slot
+  int64_t *d_doff = nullptr, *d_off_ph = nullptr;
+  int64_t* d_bond4 = nullptr;   // k_cr_pair_force: per bond its G12 offsets and pairing-entry offsets
+  int *d_fill_all = nullptr, *d_fill_step = nullptr;
+  // the pool's level-0 pairing entries already hold the current Δ (set by a
+  // drifting k_cr_pair_force, consumed by the next factorisation); every
+  // other path that changes Δ leaves it false
+  bool pairing_in_pool = false;
+  bool pending = false;    // dwh_hmc_trajectory done, dwh_hmc_finish not yet
+  int async_rc = 0;        // eig path: a rocSOLVER / rocBLAS call refused while enqueuing
+
+  // transport / spectra measurement (device side allocated on first use): host
+  // copies of the x-current operator J (CSR of its imaginary parts, duplicates
+  // summed, src/Observables.jl:237-283) and of the +x, +x+y, +x-y neighbours;
+  // the rocBLAS handle (rocSOLVER zheevd, zgemm) runs on ctx->stream
+  std::vector<int> tr_nbr, tr_rowptr, tr_col;
+  std::vector<double> tr_val;
+  int tr_slots = 0;   // chains the per-chain transport buffers hold
+  rocblas_handle blas = nullptr;
+  dwh::TrBufs tr{};
+  int *d_tr_nbr = nullptr, *d_tr_rowptr = nullptr, *d_tr_col = nullptr, *d_tr_info = nullptr;
+  int* d_tr_bad = nullptr;   // eigen_solve: non-finite E / U after zheevd
+  double* d_tr_val = nullptr;
+  double* d_tr_offd = nullptr;   // zheevd off-diagonal workspace (2N)
+  int64_t tr_nw = -1, tr_nd = -1;   // ω / DOS grid lengths the output buffers hold
+  double2* d_tr_stage = nullptr;     // Δ snapshots of dwh_measure_transport_deltas
+  int64_t tr_nstage = 0;
+  // own eigensolver (dwhmc_eig.hip) workspace for eig_slots matrices: hemv
+  // partials, v ping-pong, w, tridiagonal (d, e), tau, compact-WY T blocks and
+  // the back-transform's two nb x n products; the n x n work lives in the
+  // slots' JU (A -> V), Jmn and U (eigenvector / LU scratch) buffers
+  int eig_slots = 0;
+  double2 *d_eig_part = nullptr, *d_eig_vv = nullptr, *d_eig_ww = nullptr, *d_eig_tau = nullptr;
+  double2 *d_eig_T = nullptr, *d_eig_W = nullptr, *d_eig_W2 = nullptr, *d_eig_dpart = nullptr;
+  double2* d_eig_pfin = nullptr;   // the hemv partials reduced per row (k_eig_reduce)
+  double2* d_eig_colfin = nullptr;   // column i with its pending pairs (k_eig_reduce)
+  double2* d_eig_gpart = nullptr;    // k_eig_reduce's g partials (one matrix)
+  int* d_eig_c0 = nullptr;         // particle-hole half solve: first computed eigenvector per matrix
+  bool eig_half = false;           // the last own solve ran the particle-hole half solve
+  std::vector<int> eig_c0h;        // its c0 per matrix (N: no zero crowding)
+  // the last eigen_solve's U of every slot is closed under the particle-hole
+  // map column by column (half solve, c0 = N everywhere, no fallback):
+  // transport's pair sums then run over half the pairs
+  bool eig_ph = false;
+  int64_t eig_long_clusters = 0;   // clusters longer than k_eig_orth's limit, orthonormalised by long_clusters
+  int eig_ph_last = -1;    // dwh_info_t::eig_half: eig_ph of the last eigensolve (-1: none yet)
+  int eig_quat_last = 0;   // the last eigensolve took the structure-preserving solver
+  double *d_eig_d = nullptr, *d_eig_e = nullptr, *d_eig_tn = nullptr;
+  // structure-preserving solver (dwhmc_qeig.hip) workspace: q_slots matrices
+  // (q_bufs), the eigenvector stage's for q_vec_slots (q_heev_enqueue)
+  double* d_q = nullptr;
+  int q_slots = 0, q_vec_slots = 0;
+  double2 *d_qz = nullptr, *d_qs = nullptr, *d_qg = nullptr;
+  hipStream_t eig_sx[3] = {};       // extra streams of the sub-batched tridiagonalisation
+  hipEvent_t eig_ev[4] = {};
+
+  // timing
+  int timing = 0;   // bitmask over TimerName (bit i = kTimerNames[i])
+  std::vector<dwh::TimingRec> recs;
+  std::vector<hipEvent_t> pool;
+  double t_ms[dwh::T_COUNT] = {0};
+  int64_t t_n[dwh::T_COUNT] = {0};
+  double t_work[dwh::T_COUNT] = {0};
+};
+
+namespace dwh {
+
+// ctx == nullptr: the text goes where dwh_last_error(NULL) reads it (dwhmc_model.h)
+inline int fail(dwh_ctx* ctx, int code, const std::string& msg) {
+  if (ctx) ctx->err = msg;
+  else g_create_error = msg;
+  return code;
+}
+
+#define HIPCHECK(ctx, x)                                                                  \
+  do {                                                                                    \
+    hipError_t e_ = (x);                                                                  \
+    if (e_ != hipSuccess)                                                                 \
+      return fail((ctx), DWH_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+int settle(dwh_ctx* ctx);   // dwhmc_api.cpp
+// finish (and recover) pending throughput sweeps before the state is read or changed
+#define SETTLE(ctx)                                 \
+  do {                                              \
+    if (!(ctx)->enq.empty())                        \
+      if (int rc_ = settle(ctx)) return rc_;        \
+  } while (0)
+
+template <typename T>
+int dalloc(dwh_ctx* ctx, T** p, size_t n) {
+  void* q = nullptr;
+  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+  hipError_t e = hipMalloc(&q, bytes);
+  if (e != hipSuccess)
+    return fail(ctx, DWH_ERR_HIP, "hipMalloc(" + std::to_string(bytes) + " B): " + hipGetErrorString(e));
+  ctx->allocations.push_back(q);
+  ctx->device_bytes += (int64_t)bytes;
+  *p = static_cast<T*>(q);
+  return DWH_OK;
+}
+
+inline void drop_alloc(dwh_ctx* ctx, void* p) {
+  if (!p) return;
+  auto it = std::find(ctx->allocations.begin(), ctx->allocations.end(), p);
+  if (it != ctx->allocations.end()) ctx->allocations.erase(it);
+  (void)hipFree(p);
+}
+
+inline hipEvent_t take_event(dwh_ctx* ctx) {
+  if (!ctx->pool.empty()) {
+    hipEvent_t e = ctx->pool.back();
+    ctx->pool.pop_back();
+    return e;
+  }
+  hipEvent_t e;
+  // no system-scope fence per record: the timers bracket device kernels only,
+  // and the fence's L2 writeback would perturb the kernels being timed
+  (void)hipEventCreateWithFlags(&e, hipEventDisableSystemFence);
+  return e;
+}
+
+struct Scope {
+  dwh_ctx* ctx;
+  int name;
+  double work;
+  hipStream_t st;
+  hipEvent_t a{};
+  bool on;
+  Scope(dwh_ctx* c, int n, double w)
+      : ctx(c), name(n), work(w), st(c->stream), on(((c->timing >> n) & 1) != 0) {
+    if (on) {
+      a = take_event(ctx);
+      (void)hipEventRecord(a, st);
+    }
+  }
+  ~Scope() {
+    if (on) {
+      hipEvent_t b = take_event(ctx);
+      (void)hipEventRecord(b, st);
+      ctx->recs.push_back({name, a, b, work});
+    }
+  }
+};
+
+inline void drain_timing(dwh_ctx* ctx) {
+  if (ctx->recs.empty()) return;
+  (void)hipStreamSynchronize(ctx->stream);
+  for (auto& r : ctx->recs) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, r.a, r.b);
+    ctx->t_ms[r.name] += ms;
+    ctx->t_n[r.name] += 1;
+    ctx->t_work[r.name] += r.work;
+    ctx->pool.push_back(r.a);
+    ctx->pool.push_back(r.b);
+  }
+  ctx->recs.clear();
+}
+
+// dwhmc_measure.cpp, called from the step and creation code as well:
+// device buffers (+ the rocBLAS handle) of `slots` measurement slots
+int transport_prepare(dwh_ctx* ctx, int64_t nw, int64_t nd, int slots);
+// where the slots of a batched eigensolve take their H_BdG(Δ) from: slot k
+// assembles Δ = Delta + k dstride with the hopping / disorder of chain
+// chain0 + k cstep
+struct TrSrc {
+  const double2* Delta;
+  int64_t dstride;
+  int64_t chain0;
+  int cstep;
+};
+TrSrc chains_src(const dwh_ctx* ctx, int64_t c0);
+int eigen_solve(dwh_ctx* ctx, const TrSrc& src, int m);
+int eigen_info_check(dwh_ctx* ctx, int m);
+
+}  // namespace dwh

@@ -46,6 +46,7 @@ __device__ __forceinline__ double2 cinv_fast(double2 a) {
 // Bijective XCD-aware remap of a 1D grid (cdna_hip_programming.md §5): blocks
 // b and b+8 share an XCD, so item ranges [x*q, (x+1)*q) are given to one XCD
 // and neighbouring rows of one matrix share that XCD's L2.  Speed only.
+// Host twin: xcd_remap_host (dwhmc_plan.cpp), which orders the product slots.
 __device__ __forceinline__ int xcd_remap(int orig, int total) {
   const int q = total / 8, r = total % 8, xcd = orig % 8;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;

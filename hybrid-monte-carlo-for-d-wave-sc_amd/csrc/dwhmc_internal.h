@@ -1,5 +1,7 @@
-// Internal launch interface between the C-ABI context (dwhmc_api.cpp) and the
-// gfx950 kernels (dwhmc_kernels.hip).  Not part of the public ABI.
+// Internal launch interface between the C-ABI context (dwhmc_api.cpp: steps,
+// creation, HMC; dwhmc_measure.cpp: eigensolver driver and transport;
+// dwhmc_plan.cpp: the cyclic-reduction plan) and the gfx950 kernels
+// (dwhmc_*.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -85,7 +87,7 @@ static_assert(sizeof(CrSlot) == 64 && offsetof(CrSlot, out) == 8 && offsetof(CrS
 inline int cr_task_tiles(const CrTask& t, int ts) {
   return ((t.r1 + ts - 1) / ts - t.r0 / ts) * ((t.c1 + ts - 1) / ts - t.c0 / ts);
 }
-bool cr_supported_bp(int BP);
+inline bool cr_supported_bp(int BP) { return BP == 32 || BP == 64 || BP == 96 || BP == 128; }
 // diagnostic stamp builds (-DCR_STAMPS, dwh_debug_cr_stamps): workgroups recorded per launch
 constexpr int kCrStampWG = 2048;
 #ifdef CR_STAMPS
@@ -125,7 +127,7 @@ void launch_cr_inv(const CrDims& c, double2* pool, const int* blk, const int* ds
                    int n, double* ldpart, hipStream_t s, const SiteGuard& sg = SiteGuard{});
 // level-0 inversions of blocks blk[i] (BP = 32, 64, 96) from the static R = A^-1
 // blocks rblk[i] (k_cr_inv0); ln|det| = ldA/2 + ln|det S| into ldpart slots
-bool cr_supported_inv0(int BP);
+inline bool cr_supported_inv0(int BP) { return BP == 64 || BP == 32 || BP == 96; }
 // Delta != nullptr: one extra workgroup per chain checks the site guard
 // (Σ of |Δ| over each site's 4 bonds site4[4 i ..] <= cap4, else *flag = 1)
 void launch_cr_inv0(const CrDims& c, double2* pool, const int* blk, const int* rblk, const int* dst,
@@ -135,7 +137,7 @@ void launch_cr_inv0(const CrDims& c, double2* pool, const int* blk, const int* r
 // the same inversions plus nst side-work product tasks per batch item
 // (32 x 32 wave tiles, maxt32 per task, each task's sign in bq & kCrNegBit)
 // on the CUs the inversions leave idle
-bool cr_supported_side(int BP);
+inline bool cr_supported_side(int BP) { return BP == 64; }
 void launch_cr_inv_side(const CrDims& c, double2* pool, const int* blk, const int* dst, const int* slot,
                         int n, double* ldpart, const CrTask* stasks, int nst, int maxt32, hipStream_t s,
                         const SiteGuard& sg = SiteGuard{});
@@ -144,7 +146,7 @@ void launch_cr_inv_side(const CrDims& c, double2* pool, const int* blk, const in
 // entry); rowpat / colpat hold them per pool block ([block][entry][BP], entry
 // = top-half offset | index << 14 | op << 22, op 3 empty; dwhmc_cr_sparse.hip)
 constexpr int kCrSpNZ = 4;
-bool cr_supported_sparse0(int BP);
+inline bool cr_supported_sparse0(int BP) { return BP == 32 || BP == 64 || BP == 96; }
 // forward, per kept row k (er = k+1, el = k-1): D'_k = D_k + V1r L_k + V2l U_el,
 // U'_k = V1r U_er, L'_k = V2r L_k with V1r = -U_k Dinv_er, V2r = -L_er Dinv_er,
 // V2l = -L_el Dinv_el (pool block indices)
@@ -173,16 +175,8 @@ void launch_cr_sp_bwd(const CrDims& c, double2* pool, const CrSpBwd* tasks, int 
 struct CrGemmCfg {
   int ts, ksplit;
 };
-// tile pairs of a stage (CrTile::pad1 = the second tile's column, -1 single), one per wave
-// maxt32 / maxt16: the largest cr_task_tiles over the stage's tasks at ts = 32 / 16;
-// ntmax: the largest term count
-CrGemmCfg cr_gemm_config(const CrDims& c, int ntasks, int maxt32, int maxt16, int ntmax, int ntiles16);
-// 16 x 16 stages (cfg.ts == 16): the dispatch-ordered slots of the stage's
-// (task, tile) list tl16 (ntl16 entries per batch item) over every batch item,
-// a whole number of workgroups (cr_gemm_slot_wgs of them)
-int cr_gemm_slot_wgs(const CrDims& c, int ntl16, const CrGemmCfg& cfg);
-void cr_gemm_slots(const CrDims& c, const CrTile* tl16, int ntl16, const CrGemmCfg& cfg, CrSlot* out);
-// slots: the stage's cr_gemm_slots (16 x 16 stages); tasks: 32 x 32 stages
+// (chosen per stage by cr_gemm_config, dwhmc_plan.h)
+// slots: the stage's cr_gemm_slots (16 x 16 stages, dwhmc_plan.h); tasks: 32 x 32 stages
 void launch_cr_gemm(const CrDims& c, double2* pool, const CrTask* tasks, int ntasks, int maxt32,
                     int maxt16, const CrSlot* slots, int nslot_wgs, const CrGemmCfg& cfg, double sg,
                     hipStream_t s);

@@ -1,0 +1,88 @@
+// The cyclic-reduction plan of the C-ABI context (dwhmc_plan.cpp): the stage
+// list build_cr_plan derives from the lattice, the sparse level-0 operand
+// arrays and the dispatch-ordered slots of the 16 x 16 product stages.  Pure
+// host index arithmetic: needs no device.  Not part of the public ABI.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "dwhmc_internal.h"
+
+namespace dwh {
+
+// One stage of the cyclic-reduction plan: a batch of block inversions or a
+// task list of block products (all batch items at once).
+struct CrStage {
+  int kind;        // 0 inversion, 1 products
+  int first, n;    // range in CrPlan::inv_blk / CrPlan::tasks
+  double sg;       // products: sign of the sum
+  double flops;    // products: algorithmic fp64 flops per batch item (restricted ranges)
+  int maxt32, maxt16, ntmax;
+  int tfirst, ntiles;   // products: range in CrPlan::tiles16 (the stage's (task, tile) pairs);
+                        // inversions: their side-work tasks in CrPlan::tasks (launch_cr_inv_side,
+                        // maxt32 tiles each), flops in `flops`
+  dwh::CrGemmCfg cfg;   // products: tile / K-split chosen once per context
+  int sfirst = 0, nswg = 0;   // 16 x 16 products: their dispatch-ordered slots (CrPlan::slots, nswg workgroups)
+  int l0 = 0;           // inversions: level 0 from the static R = A^-1 blocks (k_cr_inv0)
+  int sp = 0;           // kind 2 (sparse level-0 stage): 0 forward (CrPlan::sp_fwd), 1 backward (sp_bwd)
+};
+
+struct CrPlan {
+  int nblk = 0;
+  std::vector<CrStage> stages;
+  std::vector<dwh::CrTask> tasks;
+  std::vector<dwh::CrTile> tiles16;          // per product stage: its 16 x 16 tiles with their operands
+  std::vector<dwh::CrSlot> slots;            // per 16 x 16 product stage: its tiles of every batch item,
+                                             // dispatch order (dwh::cr_gemm_slots; built with the stage configs)
+  std::vector<int> inv_blk, inv_dst, inv_slot;   // inversion source / destination block, ln|det| slot
+  std::vector<int> inv0_r;                       // level-0 inversions (l0 stage): R = A^-1 block per entry
+  std::vector<int64_t> goff, doff;
+  std::vector<int> fill_all, fill_step;      // level-0 blocks written at create / every step
+  std::vector<int64_t> off_ph;               // pairing entries outside fill_step (-1: none)
+  int n_ph = 0;                              // entries of off_ph >= 0
+  // sparse level 0 (dwhmc_cr_sparse.hip): the stages' tasks and the level-0
+  // U / L patterns (CrPlan::rowpat / colpat: [3 Ly][kCrSpNZ][BP])
+  std::vector<dwh::CrSpFwd> sp_fwd;
+  std::vector<dwh::CrSpBwd> sp_bwd;
+  std::vector<int> rowpat, colpat;
+};
+
+// The sparse stages' per-task operand arrays (launch_cr_sp_fwd / _bwd,
+// dwhmc_internal.h).  Per task: the row-pattern words of its left sparse
+// operands, laid out [row r < HP][operand][entry] so a wave reads its row's
+// words (and then their values) with scalar loads (row); and the column
+// entries of its right operands, [operand][entry][column], value (cv) and
+// meta word (cm: Δ index + 1 | op << 22 | row << 24), read coalesced.
+// Forward tasks first; the backward ones from row_bwd0 / col_bwd0.
+struct SpTaskArrays {
+  std::vector<int> row, cm;
+  std::vector<double2> cv;
+  size_t row_bwd0 = 0, col_bwd0 = 0;
+};
+
+SpTaskArrays cr_sparse_task_arrays(const CrPlan& pl, int BP, const std::vector<double2>& colval,
+                                   const std::vector<int>& colsrc);
+// column-pattern values of the level-0 U / L blocks (static hopping value, or
+// the Δ index of a pairing entry) in the kernels' [block][entry][BP] order
+void cr_sparse_colvals(const std::vector<int>& colpat, int Lx, int Ly, int BP, const std::vector<int>& hcol,
+                       const std::vector<double>& hval, const std::vector<int>& Dcol, const std::vector<int>& Dsrc,
+                       std::vector<double2>& colval, std::vector<int>& colsrc);
+// lattice rows per CR block
+int cr_rows_per_block(int64_t Lx, int64_t Ly);
+// the plan of an Lx x Ly CR lattice of BP-wide blocks (dwhmc_plan.cpp)
+CrPlan build_cr_plan(int Lx, int Ly, int BP, const std::vector<int>& Dcol, bool side, int nbatch, int ncu, bool inv0,
+                     const std::vector<int>* hcol);
+// tile pairs of a stage (CrTile::pad1 = the second tile's column, -1 single), one per wave
+// maxt32 / maxt16: the largest cr_task_tiles over the stage's tasks at ts = 32 / 16;
+// ntmax: the largest term count
+CrGemmCfg cr_gemm_config(const CrDims& c, int ntasks, int maxt32, int maxt16, int ntmax, int ntiles16);
+// 16 x 16 stages (cfg.ts == 16): the dispatch-ordered slots of the stage's
+// (task, tile) list tl16 (ntl16 entries per batch item) over every batch item,
+// a whole number of workgroups (cr_gemm_slot_wgs of them)
+int cr_gemm_slot_wgs(const CrDims& c, int ntl16, const CrGemmCfg& cfg);
+void cr_gemm_slots(const CrDims& c, const CrTile* tl16, int ntl16, const CrGemmCfg& cfg, CrSlot* out);
+// DWHMC_CR_PLAN_DUMP=1: one line per stage to stderr (nbatch inversion
+// workgroups per block; cfg: the product stages' configurations are chosen)
+void cr_plan_dump(const CrPlan& pl, int64_t nbatch, bool cfg);
+
+}  // namespace dwh

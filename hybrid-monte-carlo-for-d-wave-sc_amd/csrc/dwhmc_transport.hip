@@ -5,7 +5,7 @@
 // sweeps (src/Simulation.jl:170-186), not the leapfrog hot path: the
 // eigenpairs come from the library's own Hermitian eigensolver
 // (dwhmc_eig.hip) and J_mn = U^H (J ⊕ J) U from its own batched fp64 MFMA
-// product (dwhmc_gemm.hip), both driven by dwhmc_api.cpp; the kernels here
+// product (dwhmc_gemm.hip), both driven by dwhmc_measure.cpp; the kernels here
 // are everything around them.  All matrices are column-major with leading dimension n2 = 2N (the
 // eigenvector of E_n is column n of U, as Julia's eigen! returns it).
 //

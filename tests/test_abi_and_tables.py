@@ -56,7 +56,7 @@ def test_neighbour_tables_bit_exact(dwhmc, oracle, Lx, Ly):
     assert np.array_equal(nnn, nnn_o)
 
 
-# the two compiled tables (dwhmc_api.cpp, DWHMC_POLE_TABLE): strict (2e-14) and
+# the two compiled tables (dwhmc_model.cpp, DWHMC_POLE_TABLE): strict (2e-14) and
 # the tolerance-budgeted default (5e-12)
 TABLES = ["", "_eps5e-12"]
 

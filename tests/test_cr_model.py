@@ -1,5 +1,5 @@
 """CPU check of the block cyclic-reduction algorithm the CR device path runs
-(tools/cr_model.py restates the planner of csrc/dwhmc_api.cpp build_cr_plan):
+(tools/cr_model.py restates the planner of csrc/dwhmc_plan.cpp build_cr_plan):
 ln|det| and the block-tridiagonal part of G = (H_BdG - i y)^-1 against dense
 numpy for every chain shape the planner distinguishes (Ly = 1, 2, odd levels,
 even levels, non-square)."""

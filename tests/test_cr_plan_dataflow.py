@@ -1,4 +1,5 @@
-"""CPU check of the cyclic-reduction schedule the C ABI builds (no device):
+"""CPU check of the cyclic-reduction schedule the C ABI builds (no device;
+the planner and this check are csrc/dwhmc_plan.cpp):
 dwh_debug_cr_plan_check builds the plan dwh_create would and verifies its
 dataflow -- every block a launch reads was written by an earlier launch (or
 is a level-0 / static block), no launch reads a block it writes (other than a
