@@ -1,21 +1,17 @@
 // C-ABI context of the MI355X fermionic action/force path (include/dwhmc.h):
 // context creation, the leapfrog step (Gauss-Jordan / cyclic reduction / eig),
 // the guards with their pole re-selection, and the HMC and state entry points.
-// The context struct is in dwhmc_ctx.h, the pole tables and norm bounds in
-// dwhmc_model.cpp, the cyclic-reduction plan in dwhmc_plan.cpp, the
-// eigensolver driver and the transport measurement in dwhmc_measure.cpp.
+// The context struct is in dwhmc_ctx.h, the eigensolver driver and the
+// transport measurement in dwhmc_measure.cpp.
 //
-// Host-side responsibilities, each restating a reference function:
-//   * static hopping block h from the neighbour tables with the reference's
-//     upper-triangle overwrite order        (src/Hamiltonian.jl:10-47;
-//     build_hrow, dwhmc_model.cpp)
-//   * pairing pattern D[r, c] <- Δ[src]/2 with the reference's overwrite order
-//                                            (src/Hamiltonian.jl:55-86)
-//   * pole selection from the compiled table for κ = β E'/2; beyond the
-//     table the eigendecomposition path (algo eig: the library's own
-//     eigensolver per step, dwhmc_eig.hip — the reference's own diagonalize
-//     + compute_forces!)
-//   * the per-sweep launch sequence of hmc_sweep! (src/HMC.jl:71-144)
+// Context creation is a sequence of host-only steps that live elsewhere — the
+// lattice model and the pole selection (dwhmc_model.cpp), the choice of
+// algorithm and the cyclic-reduction plan (dwhmc_plan.cpp) — followed by the
+// device side here (device_side); a pole re-selection repeats poles, plan and
+// device side on the model the context keeps.  Beyond the pole table runs the
+// eigendecomposition path (algo eig: the library's own eigensolver per step,
+// dwhmc_eig.hip — the reference's own diagonalize + compute_forces!).  The
+// per-sweep launch sequence restates hmc_sweep! (src/HMC.jl:71-144).
 // All arithmetic runs in the HIP kernels (dwhmc_kernels.hip); there is no CPU
 // fallback: a missing device is an error.
 #include <hip/hip_runtime.h>
@@ -27,7 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <map>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -251,10 +247,10 @@ void factorize_enqueue(dwh_ctx* ctx, const dwh::KickDrift& kd) {
 void fermion_energy_enqueue(dwh_ctx* ctx) {
   if (ctx->algo == ALGO_EIG) return;   // written by k_eig_gather with P
   if (ctx->algo == ALGO_CR)
-    dwh::launch_cr_fermion_energy(ctx->cr, ctx->bpool, ctx->d_doff, ctx->ldpart, ctx->d_c, ctx->Cx,
+    dwh::launch_cr_fermion_energy(ctx->cr, ctx->bpool, ctx->d_doff, ctx->ldpart, ctx->d_c, ctx->poles.Cx,
                                   ctx->beta, ctx->efpart, ctx->efdone, ctx->Ef, ctx->Trhh, ctx->stream);
   else
-    dwh::launch_fermion_energy(ctx->d, ctx->ldstatic, ctx->ldpart, ctx->diagS, ctx->d_c, ctx->Cx,
+    dwh::launch_fermion_energy(ctx->d, ctx->ldstatic, ctx->ldpart, ctx->diagS, ctx->d_c, ctx->poles.Cx,
                                ctx->beta, ctx->Ef, ctx->Trhh, ctx->stream);
 }
 
@@ -298,277 +294,36 @@ void sweep_enqueue(dwh_ctx* ctx, const double2* noise, const double* uniform, ui
                        ctx->TrhhB, ctx->Hold, ctx->Hnew, uniform, acc, dH, ctx->beta, ctx->J, mass, sh, s);
 }
 
-int create_impl(dwh_ctx** out, int64_t Lx, int64_t Ly, double t, double tp, double mu, double beta,
-                double J, const int64_t* nn, const int64_t* nnn, int64_t nchains,
-                const double* disorder, double delta_cap, int32_t algo_req, int32_t device) {
-  if (!out) return fail(nullptr, DWH_ERR_ARG, "ctx pointer is NULL");
-  *out = nullptr;
-  if (Lx < 1 || Ly < 1) return fail(nullptr, DWH_ERR_ARG, "Lx, Ly must be >= 1");
-  if (!(beta > 0)) return fail(nullptr, DWH_ERR_ARG, "beta must be > 0");
-  if (J == 0 || !std::isfinite(J)) return fail(nullptr, DWH_ERR_ARG, "J must be finite and nonzero");
-  if (nchains < 1) return fail(nullptr, DWH_ERR_ARG, "nchains must be >= 1");
-  if (!nn || !nnn || !disorder) return fail(nullptr, DWH_ERR_ARG, "NULL table or disorder");
-  const int64_t N64 = Lx * Ly;
-  if (N64 > 9216) return fail(nullptr, DWH_ERR_ARG, "N = Lx*Ly > 9216 not supported (LDS row staging)");
-  const int N = (int)N64;
-  for (int64_t e = 0; e < 4 * N64; ++e)
-    if (nn[e] < 1 || nn[e] > N64 || nnn[e] < 1 || nnn[e] > N64)
-      return fail(nullptr, DWH_ERR_ARG, "neighbour table entry out of [1, N]");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return fail(nullptr, DWH_ERR_HIP, "no HIP device available (the fermion path has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(nullptr, DWH_ERR_ARG, "device index out of range");
+// a device buffer holding a host vector; the copy is asynchronous on
+// ctx->stream, so the vector has to outlive device_side's synchronisation
+template <typename T>
+int upload(dwh_ctx* ctx, T** p, const std::vector<T>& v, const char* name) {
+  if (int rc = dalloc(ctx, p, v.size())) return rc;
+  if (!v.empty() && hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    return fail(ctx, DWH_ERR_HIP, std::string("upload ") + name);
+  return DWH_OK;
+}
 
-  auto NN = [&](int i, int dir) { return (int)(nn[(int64_t)dir * N + i] - 1); };
-  auto NNN = [&](int i, int dir) { return (int)(nnn[(int64_t)dir * N + i] - 1); };
-
-  // --- static h: reference upper-triangle loop with overwrite (Hamiltonian.jl:26-44)
-  const std::vector<std::vector<std::pair<int, double>>> hrow = build_hrow(N, t, tp, nn, nnn);
-  std::vector<int> hcol((size_t)N * kHSlots, -1);
-  std::vector<double> hval((size_t)nchains * N * kHSlots, 0.0);
-  double hmax = 0;
-  for (int i = 0; i < N; ++i) {
-    if ((int)hrow[i].size() + 1 > kHSlots)
-      return fail(nullptr, DWH_ERR_ARG, "more than 8 hopping partners per site");
-    hcol[(size_t)i * kHSlots] = i;
-    double off = 0;
-    for (size_t s = 0; s < hrow[i].size(); ++s) {
-      hcol[(size_t)i * kHSlots + 1 + s] = hrow[i][s].first;
-      off += std::fabs(hrow[i][s].second);
-    }
-    for (int64_t c = 0; c < nchains; ++c) {
-      const double w = disorder[c * N64 + i];
-      if (!std::isfinite(w)) return fail(nullptr, DWH_ERR_ARG, "non-finite disorder");
-      hval[((size_t)c * N + i) * kHSlots] = w - mu;  // Hamiltonian.jl:18-22
-      for (size_t s = 0; s < hrow[i].size(); ++s)
-        hval[((size_t)c * N + i) * kHSlots + 1 + s] = hrow[i][s].second;
-      hmax = std::max(hmax, std::fabs(w - mu) + off);
-    }
-  }
-  // --- pairing pattern with the reference overwrite order (Hamiltonian.jl:68-83)
-  std::map<std::pair<int, int>, int> dmap;
-  for (int i = 0; i < N; ++i)
-    for (int dir = 0; dir < 2; ++dir) {
-      const int j = NN(i, dir);
-      const int src = i + N * dir;
-      dmap[{i, j}] = src;
-      dmap[{j, i}] = src;
-    }
-  std::vector<int> Dcol((size_t)N * kSlots, -1), Dsrc((size_t)N * kSlots, -1);
-  std::vector<int> dcount(N, 0);
-  for (auto& kv : dmap) {
-    const int r = kv.first.first;
-    if (dcount[r] >= kSlots) return fail(nullptr, DWH_ERR_ARG, "more than 4 pairing partners per site");
-    Dcol[(size_t)r * kSlots + dcount[r]] = kv.first.second;
-    Dsrc[(size_t)r * kSlots + dcount[r]] = kv.second;
-    dcount[r]++;
-  }
-  for (auto& kv : dmap) {
-    auto it = dmap.find({kv.first.second, kv.first.first});
-    if (it == dmap.end() || it->second != kv.second)
-      return fail(nullptr, DWH_ERR_ARG, "pairing block not symmetric (unsupported table)");
-  }
-  auto slot_of = [&](int r, int c) {
-    for (int s = 0; s < kSlots; ++s)
-      if (Dcol[(size_t)r * kSlots + s] == c) return s;
-    return -1;
-  };
-  std::vector<int> bij(2 * (size_t)N), bji(2 * (size_t)N);
-  for (int dir = 0; dir < 2; ++dir)
-    for (int i = 0; i < N; ++i) {
-      const int j = NN(i, dir);
-      const int sij = slot_of(i, j), sji = slot_of(j, i);
-      if (sij < 0 || sji < 0) return fail(nullptr, DWH_ERR_ARG, "bond missing from the pairing pattern");
-      bij[(size_t)dir * N + i] = i * kSlots + sij;
-      bji[(size_t)dir * N + i] = j * kSlots + sji;
-    }
-
-  // --- pole selection: E' >= ‖H_BdG‖ <= ‖h‖ + ‖pairing block‖ with
-  // ‖h‖ <= min(Gershgorin, Lanczos bound) and the pairing block's norm <= its
-  // max row sum Σ_j |Δ_ij|/2 <= 2 delta_cap (bond guard: each of the 4 bonds
-  // <= cap; site guard: their mean <= cap)
-  // (the Lanczos bound only where certified, certify_spectral_bound)
-  hmax = h_norm_bound(hrow, disorder, mu, N, (int)Lx, (int)Ly, nchains, hmax);
-  // algorithm: explicit request, else DWHMC_ALGO = dense | cr | eig | auto
-  // (auto: cr when the lattice-row block 2 Lx fits a supported padded size,
-  // else dense; eig when κ = β E'/2 is beyond the pole table)
-  std::string want = "auto";
-  if (algo_req == DWH_ALGO_DENSE) want = "dense";
-  else if (algo_req == DWH_ALGO_CR) want = "cr";
-  else if (algo_req == DWH_ALGO_EIG) want = "eig";
-  else if (const char* e = std::getenv("DWHMC_ALGO")) want = e;
-  if (want != "auto" && want != "dense" && want != "cr" && want != "eig")
-    return fail(nullptr, DWH_ERR_ARG, "DWHMC_ALGO must be auto, dense, cr or eig");
-  // site guard on the CR path (checked by its level-0 inversion launch)
-  const bool site_guard = [&] {
-    const int BPc = (int)(2 * ((Lx + 15) / 16 * 16));
-    return want == "cr" || (want == "auto" && dwh::cr_supported_bp(BPc));
-  }();
-  if (delta_cap <= 0) delta_cap = default_delta_cap(beta, J, site_guard);
-  const double Eb = hmax + 2.0 * delta_cap;
-  const double kneed = 0.5 * beta * Eb;
-  std::string terr;
-  const PoleTable* tab = pole_table(&terr);
-  if (!tab) return fail(nullptr, DWH_ERR_ARG, terr);
-  int sel = -1;
-  for (int e = 0; e < tab->size; ++e)
-    if (tab->at(e).kappa >= kneed * (1.0 - 1e-12)) {
-      sel = e;
-      break;
-    }
-  if (sel < 0 && want == "auto") want = "eig";
-  if (sel < 0 && want != "eig") {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "beta*E_bound/2 = %g exceeds the pole table (max kappa %g)", kneed,
-                  tab->at(tab->size - 1).kappa);
-    return fail(nullptr, DWH_ERR_TABLE, buf);
-  }
-  const bool eig = want == "eig";
-  // the eigen path is exact for any Δ: no pole set, no |Δ| guard
-  if (eig) delta_cap = std::numeric_limits<double>::max();
-  const PoleView pv = eig ? PoleView{} : tab->at(sel);
-  const PoleView* pe = eig ? nullptr : &pv;
-  const double kappa = eig ? kneed : pe->kappa;
-  const double Ep = eig ? Eb : 2.0 * kappa / beta;
-  const int npole = eig ? 1 : pe->m;   // eig: one dummy batch item per chain
-  std::vector<double> y(npole, 0.0), cq(npole, 0.0);
-  double suma = 0;
-  for (int q = 0; q < (eig ? 0 : npole); ++q) {
-    y[q] = Ep * std::sqrt(pe->t[q]);
-    cq[q] = 0.5 * pe->a[q] * Ep;
-    suma += pe->a[q];
-  }
-
-  dwh_ctx* ctx = new dwh_ctx();
-  ctx->nn_host.assign(nn, nn + 4 * N64);
-  ctx->nnn_host.assign(nnn, nnn + 4 * N64);
-  ctx->dis_host.assign(disorder, disorder + nchains * N64);
-  ctx->device = device;
-  ctx->Lx = Lx;
-  ctx->Ly = Ly;
-  ctx->t = t;
-  ctx->tp = tp;
-  ctx->mu = mu;
-  ctx->beta = beta;
-  ctx->J = J;
-  ctx->delta_cap = delta_cap;
-  ctx->site_guard = site_guard && !eig;
-  // x-current operator J [src/Observables.jl:237-283]: i t at (i, i+x), i t' at
-  // (i, i+x+y) and (i, i+x-y), plus their conjugate transposes, summed into CSR
-  // (SparseArrays.sparse adds duplicates); stored as imaginary parts
-  {
-    std::vector<std::map<int, double>> jrow(N);
-    ctx->tr_nbr.assign(3 * (size_t)N, 0);
-    for (int i = 0; i < N; ++i) {
-      const int js[3] = {NN(i, 0), NNN(i, 0), NNN(i, 3)};
-      const double ts[3] = {t, tp, tp};
-      for (int b = 0; b < 3; ++b) {
-        jrow[i][js[b]] += ts[b];
-        jrow[js[b]][i] -= ts[b];
-        ctx->tr_nbr[(size_t)b * N + i] = js[b];
-      }
-    }
-    ctx->tr_rowptr.assign(N + 1, 0);
-    for (int r = 0; r < N; ++r) {
-      for (auto& kv : jrow[r]) {
-        ctx->tr_col.push_back(kv.first);
-        ctx->tr_val.push_back(kv.second);
-      }
-      ctx->tr_rowptr[r + 1] = (int)ctx->tr_col.size();
-    }
-  }
-  ctx->kappa = kappa;
-  ctx->Ebound = Ep;
-  ctx->hmax = hmax;
-  ctx->err_tanh = eig ? 0.0 : pe->err_tanh;
-  ctx->Cx = eig ? 0.0 : pe->C_u - kappa * std::log(Ep) * suma;
-  ctx->y = y;
-  ctx->cq = cq;
-  Dims& d = ctx->d;
-  d.N = N;
-  d.Np = ((N + kGJ - 1) / kGJ) * kGJ;
-  d.nb = d.Np / kGJ;
-  d.nc = (int)nchains;
-  d.P = npole;
-  d.nbatch = d.nc * d.P;
-  d.mat = (int64_t)d.Np * d.Np;
-  d.nld = d.nb;
-  {
-    const bool ok = dwh::cr_supported_bp((int)(2 * ((Lx + 15) / 16 * 16)));
-    // the CR lattice: R lattice rows per block (cr_rows_per_block)
-    const int rows = ok ? cr_rows_per_block(Lx, Ly) : 1;
-    const int Lxc = (int)Lx * rows, Lyc = (int)Ly / rows;
-    const int BP = 2 * ((Lxc + 15) / 16 * 16);   // top halves HP x BP, HP = Lxc rounded to 16
-    if (want == "cr" && !ok) {
-      ctx->err = "DWHMC_ALGO=cr needs 2*Lx <= 128";
-      g_create_error = ctx->err;
-      delete ctx;
-      return DWH_ERR_ARG;
-    }
-    ctx->algo = eig ? ALGO_EIG : (want == "dense" || !ok) ? ALGO_DENSE : ALGO_CR;
-    if (ctx->algo == ALGO_CR) {
-      // DWHMC_CR_SIDE=0: every product on its own stage (A/B runs, tests)
-      const char* es = std::getenv("DWHMC_CR_SIDE");
-      const bool side = dwh::cr_supported_side(BP) && !(es && *es == '0');
-      int ncu = 256;
-      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0)
-        ncu = 256;
-      // DWHMC_CR_INV0=0: level-0 blocks inverted whole (k_cr_inv) like the rest
-      const char* e0 = std::getenv("DWHMC_CR_INV0");
-      const bool inv0 = dwh::cr_supported_inv0(BP) && !(e0 && *e0 == '0');
-      ctx->plan = build_cr_plan(Lxc, Lyc, BP, Dcol, side, d.nbatch, ncu, inv0, &hcol);
-      dwh::CrDims& c = ctx->cr;
-      c.Lx = Lxc;
-      c.Ly = Lyc;
-      c.N = N;
-      c.BP = BP;
-      c.P = d.P;
-      c.nbatch = d.nbatch;
-      c.nblk = ctx->plan.nblk;
-      c.item = (int64_t)c.nblk * (BP / 2) * BP;
-      // DWHMC_CR_INV32=0: BP = 32 inversions by k_cr_inv<2> (A/B knob)
-      const char* e32 = std::getenv("DWHMC_CR_INV32");
-      c.inv32 = !(e32 && *e32 == '0');
-      d.nld = Lyc;
-      if ((uint64_t)c.item >= (uint64_t)dwh::kCrNone) {
-        ctx->err = "CR pool: a batch item exceeds 2^32 elements (32-bit block-product offsets)";
-        g_create_error = ctx->err;
-        delete ctx;
-        return DWH_ERR_ARG;
-      }
-      CrPlan& pl = ctx->plan;
-      pl.slots.clear();
-      for (CrStage& st : pl.stages) {
-        if (st.kind != 1) continue;
-        st.cfg = dwh::cr_gemm_config(c, st.n, st.maxt32, st.maxt16, st.ntmax, st.ntiles);
-        if (st.cfg.ts != 16) continue;
-        st.nswg = dwh::cr_gemm_slot_wgs(c, st.ntiles, st.cfg);
-        st.sfirst = (int)pl.slots.size();
-        pl.slots.resize(pl.slots.size() + (size_t)st.nswg * (4 / st.cfg.ksplit));
-        dwh::cr_gemm_slots(c, pl.tiles16.data() + st.tfirst, st.ntiles, st.cfg, pl.slots.data() + st.sfirst);
-      }
-      cr_plan_dump(pl, d.nbatch, true);
-    }
-  }
-
-  auto bail = [&](int code) {
-    g_create_error = ctx->err;
-    dwh_destroy(ctx);
-    return code;
-  };
-  if (hipSetDevice(device) != hipSuccess) {
-    ctx->err = "hipSetDevice failed";
-    return bail(DWH_ERR_HIP);
-  }
-  if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-    ctx->err = "hipStreamCreate failed";
-    return bail(DWH_ERR_HIP);
-  }
+// The device side of a context whose host side (model, poles, dimensions,
+// plan) is complete: stream, buffers, uploads, the zeroed cache and the static
+// initialisation.  On an error the caller destroys the context.
+int device_side(dwh_ctx* ctx) {
+  const HostModel& m = *ctx->model;
+  const Dims& d = ctx->d;
+  const int N = d.N;
+  const CrPlan& pl = ctx->plan;
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DWH_ERR_HIP, "hipSetDevice failed");
+  if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess)
+    return fail(ctx, DWH_ERR_HIP, "hipStreamCreate failed");
+  hipStream_t s = ctx->stream;
   const size_t nmat = (size_t)d.nbatch * d.mat;
   const size_t nbond = (size_t)d.nc * 2 * N;
+  std::vector<int64_t> bond4;
   int rc = DWH_OK;
 #define ALLOC(p, n) \
-  if ((rc = dalloc(ctx, &ctx->p, (n))) != DWH_OK) return bail(rc)
+  if ((rc = dalloc(ctx, &ctx->p, (n))) != DWH_OK) return rc
+#define UPLOAD(p, v) \
+  if ((rc = upload(ctx, &ctx->p, (v), #p)) != DWH_OK) return rc
   if (ctx->algo == ALGO_DENSE) {
     ALLOC(R, nmat);
     ALLOC(S, nmat);
@@ -580,50 +335,57 @@ int create_impl(dwh_ctx** out, int64_t Lx, int64_t Ly, double t, double tp, doub
     ALLOC(XR2, npanel);
     ALLOC(Pb1, (size_t)d.nbatch * kGJ * kGJ);
     ALLOC(Pb2, (size_t)d.nbatch * kGJ * kGJ);
-  } else if (ctx->algo == ALGO_CR) {
-    const CrPlan& pl = ctx->plan;
-    ALLOC(bpool, (size_t)d.nbatch * ctx->cr.item);
-    ALLOC(d_tasks, pl.tasks.size());
-    ALLOC(d_slots, pl.slots.size());
-    ALLOC(d_sp_fwd, pl.sp_fwd.size());
-    ALLOC(d_sp_bwd, pl.sp_bwd.size());
-    if (!pl.colpat.empty()) {
-      std::vector<double2> colval;
-      std::vector<int> colsrc;
-      cr_sparse_colvals(pl.colpat, ctx->cr.Lx, ctx->cr.Ly, ctx->cr.BP, hcol, hval, Dcol, Dsrc, colval, colsrc);
-      ctx->sp_arr = cr_sparse_task_arrays(pl, ctx->cr.BP, colval, colsrc);
-    }
-    ALLOC(d_sp_row, ctx->sp_arr.row.size());
-    ALLOC(d_sp_cv, ctx->sp_arr.cv.size());
-    ALLOC(d_sp_cm, ctx->sp_arr.cm.size());
-    ALLOC(efpart, 2 * (size_t)d.nbatch);
-    ALLOC(efdone, (size_t)d.nc);
-    ALLOC(d_inv_blk, pl.inv_blk.size());
-    ALLOC(d_inv_dst, pl.inv_dst.size());
-    ALLOC(d_inv_slot, pl.inv_slot.size());
-    ALLOC(d_inv0_r, pl.inv0_r.size());
-    ALLOC(ldA, (size_t)d.nbatch * ctx->cr.Ly);
-    ALLOC(d_doff, pl.doff.size());
-    ALLOC(d_off_ph, pl.off_ph.size());
-    ALLOC(d_bond4, 4 * bij.size());
-    ALLOC(d_fill_all, pl.fill_all.size());
-    ALLOC(d_fill_step, pl.fill_step.size());
-  }
-  if (ctx->algo == ALGO_DENSE) {
     ALLOC(Dv, (size_t)d.nc * N * kSlots);
     ALLOC(G12nn, (size_t)d.nbatch * N * kSlots);
     ALLOC(diagS, (size_t)d.nbatch * N);
+  } else if (ctx->algo == ALGO_CR) {
+    ALLOC(bpool, (size_t)d.nbatch * ctx->cr.item);
+    UPLOAD(d_tasks, pl.tasks);
+    UPLOAD(d_slots, pl.slots);
+    UPLOAD(d_sp_fwd, pl.sp_fwd);
+    UPLOAD(d_sp_bwd, pl.sp_bwd);
+    if (!pl.colpat.empty()) {
+      std::vector<double2> colval;
+      std::vector<int> colsrc;
+      cr_sparse_colvals(pl.colpat, ctx->cr.Lx, ctx->cr.Ly, ctx->cr.BP, m.hcol, m.hval, m.Dcol, m.Dsrc, colval, colsrc);
+      ctx->sp_arr = cr_sparse_task_arrays(pl, ctx->cr.BP, colval, colsrc);
+    }
+    UPLOAD(d_sp_row, ctx->sp_arr.row);
+    UPLOAD(d_sp_cv, ctx->sp_arr.cv);
+    UPLOAD(d_sp_cm, ctx->sp_arr.cm);
+    ALLOC(efpart, 2 * (size_t)d.nbatch);
+    ALLOC(efdone, (size_t)d.nc);
+    UPLOAD(d_inv_blk, pl.inv_blk);
+    UPLOAD(d_inv_dst, pl.inv_dst);
+    UPLOAD(d_inv_slot, pl.inv_slot);
+    UPLOAD(d_inv0_r, pl.inv0_r);
+    ALLOC(ldA, (size_t)d.nbatch * ctx->cr.Ly);
+    UPLOAD(d_doff, pl.doff);
+    UPLOAD(d_off_ph, pl.off_ph);
+    // per bond b (2N of them): G12[i, j], G12[j, i] and the pairing entries
+    // it writes (Dsrc picks the bond whose value an entry holds)
+    bond4.resize(4 * m.bij.size());
+    for (size_t b = 0; b < m.bij.size(); ++b) {
+      const int e1 = m.bij[b], e2 = m.bji[b];
+      bond4[4 * b] = pl.goff[e1];
+      bond4[4 * b + 1] = pl.goff[e2];
+      bond4[4 * b + 2] = m.Dsrc[e1] == (int)b ? pl.off_ph[e1] : -1;
+      bond4[4 * b + 3] = m.Dsrc[e2] == (int)b ? pl.off_ph[e2] : -1;
+    }
+    UPLOAD(d_bond4, bond4);
+    UPLOAD(d_fill_all, pl.fill_all);
+    UPLOAD(d_fill_step, pl.fill_step);
   }
   ALLOC(ldpart, (size_t)d.nbatch * d.nld);
   ALLOC(ldstatic, (size_t)d.nbatch);
-  ALLOC(d_y, (size_t)d.P);
-  ALLOC(d_c, (size_t)d.P);
-  ALLOC(Dcol, Dcol.size());
-  ALLOC(Dsrc, Dsrc.size());
-  ALLOC(hcol, hcol.size());
-  ALLOC(hval, hval.size());
-  ALLOC(bond_ij, bij.size());
-  ALLOC(bond_ji, bji.size());
+  UPLOAD(d_y, ctx->poles.y);
+  UPLOAD(d_c, ctx->poles.cq);
+  UPLOAD(Dcol, m.Dcol);
+  UPLOAD(Dsrc, m.Dsrc);
+  UPLOAD(hcol, m.hcol);
+  UPLOAD(hval, m.hval);
+  UPLOAD(bond_ij, m.bij);
+  UPLOAD(bond_ji, m.bji);
   ALLOC(Delta, nbond);
   ALLOC(Pi, nbond);
   ALLOC(Pair, nbond);
@@ -638,82 +400,17 @@ int create_impl(dwh_ctx** out, int64_t Lx, int64_t Ly, double t, double tp, doub
   ALLOC(Hnew, (size_t)d.nc);
   ALLOC(flag, 1);
   ALLOC(halt, 2);
-  if (ctx->site_guard) ALLOC(site4, 4 * (size_t)N);
+  if (ctx->site_guard) UPLOAD(site4, m.site4);
   ALLOC(s_noise, nbond);
   ALLOC(s_uniform, (size_t)d.nc);
   ALLOC(s_acc, (size_t)d.nc);
   ALLOC(s_dH, (size_t)d.nc);
+#undef UPLOAD
 #undef ALLOC
-  ctx->ndraws = 0;
-  hipStream_t s = ctx->stream;
-#define UP(dst, src, n)                                                                     \
-  if ((n) > 0 && hipMemcpyAsync(ctx->dst, (src), (n) * sizeof(*ctx->dst), hipMemcpyHostToDevice, s) != \
-      hipSuccess) {                                                                         \
-    ctx->err = "upload " #dst;                                                              \
-    return bail(DWH_ERR_HIP);                                                               \
-  }
-  UP(d_y, y.data(), y.size());
-  UP(d_c, cq.data(), cq.size());
-  UP(Dcol, Dcol.data(), Dcol.size());
-  UP(Dsrc, Dsrc.data(), Dsrc.size());
-  UP(hcol, hcol.data(), hcol.size());
-  UP(hval, hval.data(), hval.size());
-  UP(bond_ij, bij.data(), bij.size());
-  UP(bond_ji, bji.data(), bji.size());
-  if (ctx->site_guard) {
-    // site i: bonds (i, +x), (i, +y), (i - x, +x), (i - y, +y) in the N x 2 Δ layout
-    ctx->site4_host.resize(4 * (size_t)N);
-    for (int i = 0; i < N; ++i) {
-      ctx->site4_host[4 * i + 0] = i;
-      ctx->site4_host[4 * i + 1] = N + i;
-      ctx->site4_host[4 * i + 2] = (int)(nn[2 * N64 + i] - 1);
-      ctx->site4_host[4 * i + 3] = N + (int)(nn[3 * N64 + i] - 1);
-    }
-    UP(site4, ctx->site4_host.data(), ctx->site4_host.size());
-  }
-  // per bond b (2N of them, CR path): G12[i, j], G12[j, i] and the pairing
-  // entries it writes (Dsrc picks the bond whose value an entry holds); kept
-  // alive until the uploads below have been synchronised
-  std::vector<int64_t> bond4;
-  if (ctx->algo == ALGO_CR) {
-    const CrPlan& pl = ctx->plan;
-    bond4.resize(4 * bij.size());
-    for (size_t b = 0; b < bij.size(); ++b) {
-      const int e1 = bij[b], e2 = bji[b];
-      bond4[4 * b] = pl.goff[e1];
-      bond4[4 * b + 1] = pl.goff[e2];
-      bond4[4 * b + 2] = Dsrc[e1] == (int)b ? pl.off_ph[e1] : -1;
-      bond4[4 * b + 3] = Dsrc[e2] == (int)b ? pl.off_ph[e2] : -1;
-    }
-  }
-  if (ctx->algo == ALGO_CR) {
-    const CrPlan& pl = ctx->plan;
-    UP(d_tasks, pl.tasks.data(), pl.tasks.size());
-    UP(d_slots, pl.slots.data(), pl.slots.size());
-    UP(d_sp_fwd, pl.sp_fwd.data(), pl.sp_fwd.size());
-    UP(d_sp_bwd, pl.sp_bwd.data(), pl.sp_bwd.size());
-    UP(d_sp_row, ctx->sp_arr.row.data(), ctx->sp_arr.row.size());
-    UP(d_sp_cv, ctx->sp_arr.cv.data(), ctx->sp_arr.cv.size());
-    UP(d_sp_cm, ctx->sp_arr.cm.data(), ctx->sp_arr.cm.size());
-    UP(d_inv_blk, pl.inv_blk.data(), pl.inv_blk.size());
-    UP(d_inv_dst, pl.inv_dst.data(), pl.inv_dst.size());
-    UP(d_inv_slot, pl.inv_slot.data(), pl.inv_slot.size());
-    UP(d_inv0_r, pl.inv0_r.data(), pl.inv0_r.size());
-    UP(d_doff, pl.doff.data(), pl.doff.size());
-    UP(d_off_ph, pl.off_ph.data(), pl.off_ph.size());
-    UP(d_bond4, bond4.data(), bond4.size());
-    UP(d_fill_all, pl.fill_all.data(), pl.fill_all.size());
-    UP(d_fill_step, pl.fill_step.data(), pl.fill_step.size());
-  }
-#undef UP
   // zeroed cache, like initialize_cache (src/Types.jl:182-212): P = 0, E_f = 0
-  (void)hipMemsetAsync(ctx->Delta, 0, nbond * sizeof(double2), s);
+  for (double2* p : {ctx->Delta, ctx->Pi, ctx->Pair, ctx->F}) (void)hipMemsetAsync(p, 0, nbond * sizeof(double2), s);
+  for (double* p : {ctx->Ef, ctx->Trhh}) (void)hipMemsetAsync(p, 0, d.nc * sizeof(double), s);
   if (ctx->efdone) (void)hipMemsetAsync(ctx->efdone, 0, (size_t)d.nc * sizeof(unsigned), s);
-  (void)hipMemsetAsync(ctx->Pi, 0, nbond * sizeof(double2), s);
-  (void)hipMemsetAsync(ctx->Pair, 0, nbond * sizeof(double2), s);
-  (void)hipMemsetAsync(ctx->F, 0, nbond * sizeof(double2), s);
-  (void)hipMemsetAsync(ctx->Ef, 0, d.nc * sizeof(double), s);
-  (void)hipMemsetAsync(ctx->Trhh, 0, d.nc * sizeof(double), s);
   (void)hipMemsetAsync(ctx->flag, 0, sizeof(int), s);
   (void)hipMemsetAsync(ctx->halt, 0, 2 * sizeof(int), s);
   if (ctx->diagS) (void)hipMemsetAsync(ctx->diagS, 0, (size_t)d.nbatch * N * sizeof(double2), s);
@@ -726,24 +423,96 @@ int create_impl(dwh_ctx** out, int64_t Lx, int64_t Ly, double t, double tp, doub
     // the CR path factorises the whole BdG matrix: no static part; every
     // level-0 block written once (pairing entries 0 until the first factorize)
     (void)hipMemsetAsync(ctx->ldstatic, 0, d.nbatch * sizeof(double), s);
-    dwh::launch_cr_fill(ctx->cr, ctx->bpool, ctx->d_fill_all, (int)ctx->plan.fill_all.size(), ctx->hcol,
-                        ctx->hval, ctx->Dcol, ctx->Dsrc, ctx->Delta, ctx->d_y, nullptr, s);
+    dwh::launch_cr_fill(ctx->cr, ctx->bpool, ctx->d_fill_all, (int)pl.fill_all.size(), ctx->hcol, ctx->hval,
+                        ctx->Dcol, ctx->Dsrc, ctx->Delta, ctx->d_y, nullptr, s);
     // static R = A^-1 of the level-0 blocks k_cr_inv0 inverts: the Δ = 0
     // blocks [[A, 0], [0, -conj A]] inverted out of place give [R | 0] and
     // 2 ln|det A| (the pairing entries are still zero here)
-    for (const CrStage& st : ctx->plan.stages)
+    for (const CrStage& st : pl.stages)
       if (st.kind == 0 && st.l0)
         dwh::launch_cr_inv(ctx->cr, ctx->bpool, ctx->d_inv_blk + st.first, ctx->d_inv0_r, ctx->d_inv_slot + st.first,
                            st.n, ctx->ldA, s);
   }
-  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-    ctx->err = "static R initialisation failed on the device";
-    return bail(DWH_ERR_HIP);
-  }
+  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess)
+    return fail(ctx, DWH_ERR_HIP, "static R initialisation failed on the device");
   // eig: rocBLAS handle and the per-chain U, JU (= U diag f), ρ, E buffers
-  if (ctx->algo == ALGO_EIG && (rc = transport_prepare(ctx, 0, 0, d.nc)) != DWH_OK) return bail(rc);
+  if (ctx->algo == ALGO_EIG) return transport_prepare(ctx, 0, 0, d.nc);
+  return DWH_OK;
+}
+
+// A context on `model` for |Δ| within delta_cap (<= 0: the default cap):
+// algorithm and guard, poles, plan — all host-only, the context exists only
+// once they succeeded — then the device side.  Shared by context creation
+// and the pole re-selection, which passes the model it already holds.
+int create_on_model(dwh_ctx** out, const std::shared_ptr<const HostModel>& model, double beta, double J,
+                    double delta_cap, int32_t algo_req, int32_t device) {
+  const HostModel& m = *model;
+  AlgoChoice ac;
+  if (int rc = choose_algo(algo_req, m.Lx, m.Ly, &ac)) return rc;
+  if (delta_cap <= 0) delta_cap = default_delta_cap(beta, J, ac.site_guard);
+  PoleChoice pc;
+  if (int rc = select_poles(m.hmax, beta, delta_cap, ac.want == DWH_ALGO_EIG, ac.want == DWH_ALGO_AUTO, &pc)) return rc;
+  if (ac.want == DWH_ALGO_CR && !ac.cr_ok) return fail(nullptr, DWH_ERR_ARG, "DWHMC_ALGO=cr needs 2*Lx <= 128");
+  const int algo = pc.eig ? ALGO_EIG : (ac.want == DWH_ALGO_DENSE || !ac.cr_ok) ? ALGO_DENSE : ALGO_CR;
+  Dims d{};
+  d.N = m.N;
+  d.Np = ((m.N + kGJ - 1) / kGJ) * kGJ;
+  d.nb = d.Np / kGJ;
+  d.nc = (int)m.nchains;
+  d.P = (int)pc.y.size();   // eig: one dummy batch item per chain
+  d.nbatch = d.nc * d.P;
+  d.mat = (int64_t)d.Np * d.Np;
+  d.nld = d.nb;
+  CrDims cr{};
+  CrPlan plan;
+  if (algo == ALGO_CR) {
+    int ncu = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0) ncu = 256;
+    if (int rc = plan_cr(m.Lx, m.Ly, d.P, d.nbatch, m.Dcol, m.hcol, kCrFromEnv, kCrFromEnv, ncu, &cr, &plan)) return rc;
+    d.nld = cr.Ly;
+    cr_plan_dump(plan, d.nbatch, true);
+  }
+  dwh_ctx* ctx = new dwh_ctx();
+  ctx->model = model;
+  ctx->device = device;
+  ctx->beta = beta;
+  ctx->J = J;
+  // the eigen path is exact for any Δ: no |Δ| guard
+  ctx->delta_cap = pc.eig ? std::numeric_limits<double>::max() : delta_cap;
+  ctx->site_guard = ac.site_guard && !pc.eig;
+  ctx->poles = std::move(pc);
+  ctx->d = d;
+  ctx->algo = algo;
+  ctx->cr = cr;
+  ctx->plan = std::move(plan);
+  if (int rc = device_side(ctx)) {
+    g_create_error = ctx->err;
+    dwh_destroy(ctx);
+    return rc;
+  }
   *out = ctx;
   return DWH_OK;
+}
+
+// validate, device check (no CPU fallback: it precedes every table-derived
+// refusal), the lattice model, then create_on_model
+int create_impl(dwh_ctx** out, int64_t Lx, int64_t Ly, double t, double tp, double mu, double beta,
+                double J, const int64_t* nn, const int64_t* nnn, int64_t nchains,
+                const double* disorder, double delta_cap, int32_t algo_req, int32_t device) {
+  if (!out) return fail(nullptr, DWH_ERR_ARG, "ctx pointer is NULL");
+  *out = nullptr;
+  // the lattice size before beta and J, the rest of the lattice arguments after: the precedence callers know
+  if (Lx < 1 || Ly < 1) return fail(nullptr, DWH_ERR_ARG, "Lx, Ly must be >= 1");
+  if (!(beta > 0)) return fail(nullptr, DWH_ERR_ARG, "beta must be > 0");
+  if (J == 0 || !std::isfinite(J)) return fail(nullptr, DWH_ERR_ARG, "J must be finite and nonzero");
+  if (int rc = check_lattice_args(Lx, Ly, nchains, nn, nnn, disorder)) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    return fail(nullptr, DWH_ERR_HIP, "no HIP device available (the fermion path has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(nullptr, DWH_ERR_ARG, "device index out of range");
+  const auto model = std::make_shared<HostModel>();
+  if (int rc = build_host_model(Lx, Ly, t, tp, mu, nn, nnn, nchains, disorder, model.get())) return rc;
+  return create_on_model(out, model, beta, J, delta_cap, algo_req, device);
 }
 
 }  // namespace
@@ -802,9 +571,9 @@ int dwh_info(dwh_ctx* ctx, dwh_info_t* out) {
   out->Np = ctx->d.Np;
   out->nchains = ctx->d.nc;
   out->npoles = ctx->algo == ALGO_EIG ? 0 : ctx->d.P;
-  out->kappa = ctx->kappa;
-  out->e_bound = ctx->Ebound;
-  out->err_tanh = ctx->err_tanh;
+  out->kappa = ctx->poles.kappa;
+  out->e_bound = ctx->poles.Ep;
+  out->err_tanh = ctx->poles.err_tanh;
   out->delta_cap = ctx->delta_cap;
   out->device_bytes = ctx->device_bytes;
   out->algo = ctx->algo;
@@ -854,19 +623,16 @@ int dwh_bench_assembly(dwh_ctx* ctx, int64_t reps) {
 namespace {
 
 // Re-create the device side of `ctx` for |Δ_ij| <= new_cap: a new pole-table
-// entry for the larger spectral bound E' = hmax + 2 new_cap, same lattice,
-// disorder and algorithm; Δ, π, the throughput draws and the timing state
-// carry over.  The context is left unfactorised.
+// entry for the larger spectral bound E' = hmax + 2 new_cap and the plan for
+// its pole count, on the lattice model the context already holds (same
+// tables, ‖h‖ bound and algorithm); Δ, π, the throughput draws and the
+// timing state carry over.  The context is left unfactorised.
 int reselect_poles(dwh_ctx* ctx, double new_cap) {
   dwh_ctx* n = nullptr;
   const int32_t algo = ctx->algo == ALGO_CR ? DWH_ALGO_CR : ctx->algo == ALGO_EIG ? DWH_ALGO_EIG : DWH_ALGO_DENSE;
-  int rc = create_impl(&n, ctx->Lx, ctx->Ly, ctx->t, ctx->tp, ctx->mu, ctx->beta, ctx->J,
-                       ctx->nn_host.data(), ctx->nnn_host.data(), ctx->d.nc, ctx->dis_host.data(), new_cap,
-                       algo, ctx->device);
+  int rc = create_on_model(&n, ctx->model, ctx->beta, ctx->J, new_cap, algo, ctx->device);
   // a spectral bound beyond the pole table: the eigendecomposition path
-  if (rc == DWH_ERR_TABLE)
-    rc = create_impl(&n, ctx->Lx, ctx->Ly, ctx->t, ctx->tp, ctx->mu, ctx->beta, ctx->J, ctx->nn_host.data(),
-                     ctx->nnn_host.data(), ctx->d.nc, ctx->dis_host.data(), new_cap, DWH_ALGO_EIG, ctx->device);
+  if (rc == DWH_ERR_TABLE) rc = create_on_model(&n, ctx->model, ctx->beta, ctx->J, new_cap, DWH_ALGO_EIG, ctx->device);
   if (rc != DWH_OK)
     return fail(ctx, rc, "pole re-selection for delta_cap=" + std::to_string(new_cap) + ": " + g_create_error);
   const size_t nb = (size_t)ctx->d.nc * 2 * ctx->d.N * sizeof(double2);
@@ -935,7 +701,7 @@ int fit_cap(dwh_ctx* ctx, const dwh_c128* D, size_t n, bool* reselected = nullpt
       for (size_t i = 0; i < N; ++i) {
         double sm = 0;
         for (int k = 0; k < 4; ++k) {
-          const dwh_c128 v = D[c * 2 * N + ctx->site4_host[4 * i + k]];
+          const dwh_c128 v = D[c * 2 * N + ctx->model->site4[4 * i + k]];
           sm += std::hypot(v.re, v.im);
         }
         m = std::max(m, 0.25 * sm);
@@ -1008,7 +774,7 @@ int dwh::settle(dwh_ctx* ctx) {
                     "%s exceeded delta_cap=%g outside a logged sweep (the pole set was built for spectra "
                     "within E'=%g)",
                     ctx->site_guard ? "the mean |Delta| of a site's bonds" : "|Delta_ij|", ctx->delta_cap,
-                    ctx->Ebound);
+                    ctx->poles.Ep);
       return fail(ctx, DWH_ERR_SPECTRUM, buf);
     }
     const std::vector<dwh_ctx::EnqSweep> rest(ctx->enq.begin() + h[1], ctx->enq.end());
@@ -1464,7 +1230,7 @@ int dwh_debug_level0(dwh_ctx* ctx, int64_t chain, int64_t pole, int32_t refill, 
         }
     }
   }
-  if (y) std::copy(ctx->y.begin(), ctx->y.end(), y);
+  if (y) std::copy(ctx->poles.y.begin(), ctx->poles.y.end(), y);
   return DWH_OK;
 }
 

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -43,18 +44,15 @@ struct dwh_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   dwh::Dims d{};
-  int64_t Lx = 0, Ly = 0;
-  double t = 0, tp = 0, mu = 0, beta = 0, J = 0, delta_cap = 2.0;
+  // the lattice model (tables, ‖h‖ bound, current operator: dwhmc_model.h),
+  // built once at creation; a pole re-selection's new context shares it
+  std::shared_ptr<const dwh::HostModel> model;
+  double beta = 0, J = 0, delta_cap = 2.0;
   // guard: per site (mean |Δ| of its 4 bonds <= delta_cap, checked by the
   // level-0 inversion launch) or per bond (|Δ_ij| <= delta_cap, the drift kernels)
   bool site_guard = false;
-  std::vector<int> site4_host;   // per site: the Delta indices of its 4 bonds
-  int* site4 = nullptr;
-  double kappa = 0, Ebound = 0, Cx = 0, err_tanh = 0, hmax = 0;
-  std::vector<double> y, cq;
-  // creation inputs kept for a pole re-selection (reselect_poles)
-  std::vector<int64_t> nn_host, nnn_host;
-  std::vector<double> dis_host;
+  int* site4 = nullptr;   // device copy of the model's site4 (site guard)
+  dwh::PoleChoice poles;   // the pole set in use (select_poles)
   int reselections = 0;
   int64_t device_bytes = 0;
   bool factorized = false;
@@ -121,12 +119,10 @@ struct dwh_ctx {
   bool pending = false;    // dwh_hmc_trajectory done, dwh_hmc_finish not yet
   int async_rc = 0;        // eig path: a rocSOLVER / rocBLAS call refused while enqueuing
 
-  // transport / spectra measurement (device side allocated on first use): host
-  // copies of the x-current operator J (CSR of its imaginary parts, duplicates
-  // summed, src/Observables.jl:237-283) and of the +x, +x+y, +x-y neighbours;
-  // the rocBLAS handle (rocSOLVER zheevd, zgemm) runs on ctx->stream
-  std::vector<int> tr_nbr, tr_rowptr, tr_col;
-  std::vector<double> tr_val;
+  // transport / spectra measurement (device side allocated on first use):
+  // device copies of the model's x-current operator J (CSR) and of its +x,
+  // +x+y, +x-y neighbours; the rocBLAS handle (rocSOLVER zheevd, zgemm) runs
+  // on ctx->stream
   int tr_slots = 0;   // chains the per-chain transport buffers hold
   rocblas_handle blas = nullptr;
   dwh::TrBufs tr{};

@@ -50,18 +50,19 @@ int dwh::transport_prepare(dwh_ctx* ctx, int64_t nw, int64_t nd, int slots) {
       return fail(ctx, DWH_ERR_HIP, "rocblas_create_handle failed");
     if (rocblas_set_stream(ctx->blas, ctx->stream) != rocblas_status_success)
       return fail(ctx, DWH_ERR_HIP, "rocblas_set_stream failed");
-    if ((rc = dalloc(ctx, &ctx->d_tr_nbr, ctx->tr_nbr.size())) ||
-        (rc = dalloc(ctx, &ctx->d_tr_rowptr, ctx->tr_rowptr.size())) ||
-        (rc = dalloc(ctx, &ctx->d_tr_col, ctx->tr_col.size())) ||
-        (rc = dalloc(ctx, &ctx->d_tr_val, ctx->tr_val.size())) || (rc = dalloc(ctx, &ctx->d_tr_bad, 1)))
+    const HostModel& m = *ctx->model;
+    if ((rc = dalloc(ctx, &ctx->d_tr_nbr, m.tr_nbr.size())) ||
+        (rc = dalloc(ctx, &ctx->d_tr_rowptr, m.tr_rowptr.size())) ||
+        (rc = dalloc(ctx, &ctx->d_tr_col, m.tr_col.size())) ||
+        (rc = dalloc(ctx, &ctx->d_tr_val, m.tr_val.size())) || (rc = dalloc(ctx, &ctx->d_tr_bad, 1)))
       return rc;
     auto up = [&](void* dst, const void* src, size_t bytes) {
       return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream);
     };
-    HIPCHECK(ctx, up(ctx->d_tr_nbr, ctx->tr_nbr.data(), ctx->tr_nbr.size() * sizeof(int)));
-    HIPCHECK(ctx, up(ctx->d_tr_rowptr, ctx->tr_rowptr.data(), ctx->tr_rowptr.size() * sizeof(int)));
-    HIPCHECK(ctx, up(ctx->d_tr_col, ctx->tr_col.data(), ctx->tr_col.size() * sizeof(int)));
-    HIPCHECK(ctx, up(ctx->d_tr_val, ctx->tr_val.data(), ctx->tr_val.size() * sizeof(double)));
+    HIPCHECK(ctx, up(ctx->d_tr_nbr, m.tr_nbr.data(), m.tr_nbr.size() * sizeof(int)));
+    HIPCHECK(ctx, up(ctx->d_tr_rowptr, m.tr_rowptr.data(), m.tr_rowptr.size() * sizeof(int)));
+    HIPCHECK(ctx, up(ctx->d_tr_col, m.tr_col.data(), m.tr_col.size() * sizeof(int)));
+    HIPCHECK(ctx, up(ctx->d_tr_val, m.tr_val.data(), m.tr_val.size() * sizeof(double)));
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
   }
   if (slots > ctx->tr_slots) {
@@ -578,7 +579,7 @@ int transport_run(dwh_ctx* ctx, const TrSrc& src, int m, double eta, double dome
   const int ncol = ph ? N : n2;
   for (int k = 0; k < m; ++k) {
     const dwh::TrBufs b = tr_slot(ctx, k);
-    dwh::launch_tr_colstats(b.U, N, (int)ctx->Lx, b.E, ctx->beta, eta, ctx->t, ctx->tp, ctx->d_tr_nbr, b.f,
+    dwh::launch_tr_colstats(b.U, N, (int)ctx->model->Lx, b.E, ctx->beta, eta, ctx->model->t, ctx->model->tp, ctx->d_tr_nbr, b.f,
                             b.dia, b.Wn, b.wan, b.w0, s);
     dwh::launch_tr_current(b.U, b.JU, N, ctx->d_tr_rowptr, ctx->d_tr_col, ctx->d_tr_val, ncol, s);
   }
@@ -601,7 +602,7 @@ int transport_run(dwh_ctx* ctx, const TrSrc& src, int m, double eta, double dome
   HIPCHECK(ctx, hipGetLastError());
   const dwh::TrGrid g{eta, -omega_max, domega, (int)nw, (int)nd};
   for (int k = 0; k < m; ++k)
-    dwh::launch_tr_reduce(tr_slot(ctx, k), N, (int)ctx->Lx, (int)ctx->Ly, ctx->beta, eta, g, ph, s);
+    dwh::launch_tr_reduce(tr_slot(ctx, k), N, (int)ctx->model->Lx, (int)ctx->model->Ly, ctx->beta, eta, g, ph, s);
   HIPCHECK(ctx, hipGetLastError());
   std::vector<double> sc(2 * (size_t)m);
   HIPCHECK(ctx, hipMemcpyAsync(sc.data(), b0.scalars, sc.size() * sizeof(double), hipMemcpyDeviceToHost, s));

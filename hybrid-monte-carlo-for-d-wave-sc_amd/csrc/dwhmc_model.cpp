@@ -1,17 +1,22 @@
-// Host-only model pieces of the C-ABI context (dwhmc_model.h): pole tables,
-// the static hopping rows, the bound on ||h|| of the pole selection
-// (Gershgorin, or a certified Lanczos value) and the default guard cap.
-// No device and no vendor library: tools/host_check/plan_main.cpp links this
-// file and dwhmc_plan.cpp alone.
+// Host-only model pieces of the C-ABI context (dwhmc_model.h): the lattice
+// model (build_host_model: argument checks, hopping and pairing tables with
+// the reference's overwrite order, bond slots, the bound on ||h|| — Gershgorin
+// or a certified Lanczos value —, the x-current operator, the site guard's
+// bond list), the pole tables with the pole selection (select_poles) and the
+// default guard cap.  No device and no vendor library:
+// tools/host_check/plan_main.cpp links this file and dwhmc_plan.cpp alone and
+// checks the tables against a dense restatement of the reference.
 #include "dwhmc_model.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 
 #include "../../include/dwhmc.h"
+#include "dwhmc_internal.h"
 
 // Two compiled pole tables (tools/gen_pole_table.py): "budget", sup|tanh
 // error| <= 5e-12 — half the 1e-11 absolute budget the pairing tolerance
@@ -30,6 +35,17 @@ namespace dwh {
 thread_local std::string g_create_error;
 
 namespace {
+struct PoleView {
+  double kappa;
+  int m;
+  double C_u, err_tanh;
+  const double *t, *a;
+};
+struct PoleTable {
+  const char* name;
+  int size;
+  PoleView (*at)(int);
+};
 template <typename E>
 PoleView pole_view(const E& e, const double* T, const double* A) {
   return PoleView{e.kappa, e.m, e.C_u, e.err_tanh, T + e.off, A + e.off};
@@ -42,12 +58,50 @@ const PoleTable kPoleTables[2] = {
 };
 }  // namespace
 
-const PoleTable* pole_table(std::string* err) {
-  const char* e = std::getenv("DWHMC_POLE_TABLE");
-  if (!e || !*e || std::strcmp(e, "budget") == 0) return &kPoleTables[0];
-  if (std::strcmp(e, "strict") == 0) return &kPoleTables[1];
-  *err = "DWHMC_POLE_TABLE must be budget or strict";
-  return nullptr;
+int select_poles(double hmax, double beta, double delta_cap, bool eig_requested, bool eig_allowed, PoleChoice* out) {
+  const double Eb = hmax + 2.0 * delta_cap;
+  const double kneed = 0.5 * beta * Eb;
+  // the table DWHMC_POLE_TABLE selects (budget | strict; default budget)
+  const char* name = std::getenv("DWHMC_POLE_TABLE");
+  const PoleTable* tab = !name || !*name ? &kPoleTables[0] : nullptr;
+  for (const PoleTable& pt : kPoleTables)
+    if (name && std::strcmp(name, pt.name) == 0) tab = &pt;
+  if (!tab) return fail(nullptr, DWH_ERR_ARG, "DWHMC_POLE_TABLE must be budget or strict");
+  int sel = -1;
+  for (int e = 0; e < tab->size; ++e)
+    if (tab->at(e).kappa >= kneed * (1.0 - 1e-12)) {
+      sel = e;
+      break;
+    }
+  PoleChoice& pc = *out;
+  pc = PoleChoice{};
+  pc.eig = eig_requested || (sel < 0 && eig_allowed);
+  if (sel < 0 && !pc.eig) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "beta*E_bound/2 = %g exceeds the pole table (max kappa %g)", kneed,
+                  tab->at(tab->size - 1).kappa);
+    return fail(nullptr, DWH_ERR_TABLE, buf);
+  }
+  if (pc.eig) {   // exact for any Δ: no pole set
+    pc.kappa = kneed;
+    pc.Ep = Eb;
+    pc.y = pc.cq = {0.0};
+    return DWH_OK;
+  }
+  const PoleView pe = tab->at(sel);
+  pc.kappa = pe.kappa;
+  pc.Ep = 2.0 * pe.kappa / beta;
+  pc.y.resize(pe.m);
+  pc.cq.resize(pe.m);
+  double suma = 0;
+  for (int q = 0; q < pe.m; ++q) {
+    pc.y[q] = pc.Ep * std::sqrt(pe.t[q]);
+    pc.cq[q] = 0.5 * pe.a[q] * pc.Ep;
+    suma += pe.a[q];
+  }
+  pc.err_tanh = pe.err_tanh;
+  pc.Cx = pe.C_u - pc.kappa * std::log(pc.Ep) * suma;
+  return DWH_OK;
 }
 
 namespace {
@@ -226,6 +280,8 @@ double default_delta_cap(double beta, double J, bool site_guard) {
   return site_guard ? std::max(1.25, 4.0 * s) : std::max(2.0, 6.0 * s);
 }
 
+namespace {
+
 // ‖h‖ bound over the chains: min(Gershgorin, Lanczos) when every chain's
 // h certifies the Lanczos value, else Gershgorin
 double h_norm_bound(const std::vector<std::vector<std::pair<int, double>>>& hrow, const double* disorder, double mu,
@@ -271,34 +327,141 @@ std::vector<std::vector<std::pair<int, double>>> build_hrow(int N, double t, dou
   return hrow;
 }
 
+}  // namespace
+
+int check_lattice_args(int64_t Lx, int64_t Ly, int64_t nchains, const int64_t* nn, const int64_t* nnn,
+                       const double* disorder) {
+  if (Lx < 1 || Ly < 1) return fail(nullptr, DWH_ERR_ARG, "Lx, Ly must be >= 1");
+  if (nchains < 1) return fail(nullptr, DWH_ERR_ARG, "nchains must be >= 1");
+  if (!nn || !nnn || !disorder) return fail(nullptr, DWH_ERR_ARG, "NULL table or disorder");
+  const int64_t N64 = Lx * Ly;
+  if (N64 > 9216) return fail(nullptr, DWH_ERR_ARG, "N = Lx*Ly > 9216 not supported (LDS row staging)");
+  for (int64_t e = 0; e < 4 * N64; ++e)
+    if (nn[e] < 1 || nn[e] > N64 || nnn[e] < 1 || nnn[e] > N64)
+      return fail(nullptr, DWH_ERR_ARG, "neighbour table entry out of [1, N]");
+  return DWH_OK;
+}
+
+int build_host_model(int64_t Lx, int64_t Ly, double t, double tp, double mu, const int64_t* nn, const int64_t* nnn,
+                     int64_t nchains, const double* disorder, HostModel* out, bool lanczos) {
+  if (int rc = check_lattice_args(Lx, Ly, nchains, nn, nnn, disorder)) return rc;
+  HostModel& m = *out;
+  m = HostModel{};
+  const int N = (int)(Lx * Ly);
+  m.Lx = Lx;
+  m.Ly = Ly;
+  m.nchains = nchains;
+  m.N = N;
+  m.t = t;
+  m.tp = tp;
+  auto NN = [&](int i, int dir) { return (int)(nn[(int64_t)dir * N + i] - 1); };
+  auto NNN = [&](int i, int dir) { return (int)(nnn[(int64_t)dir * N + i] - 1); };
+
+  // --- static h: reference upper-triangle loop with overwrite (Hamiltonian.jl:26-44)
+  m.hrow = build_hrow(N, t, tp, nn, nnn);
+  const auto& hrow = m.hrow;
+  m.hcol.assign((size_t)N * kHSlots, -1);
+  m.hval.assign((size_t)nchains * N * kHSlots, 0.0);
+  for (int i = 0; i < N; ++i) {
+    if ((int)hrow[i].size() + 1 > kHSlots)
+      return fail(nullptr, DWH_ERR_ARG, "more than 8 hopping partners per site");
+    m.hcol[(size_t)i * kHSlots] = i;
+    double off = 0;
+    for (size_t s = 0; s < hrow[i].size(); ++s) {
+      m.hcol[(size_t)i * kHSlots + 1 + s] = hrow[i][s].first;
+      off += std::fabs(hrow[i][s].second);
+    }
+    for (int64_t c = 0; c < nchains; ++c) {
+      const double w = disorder[c * (int64_t)N + i];
+      if (!std::isfinite(w)) return fail(nullptr, DWH_ERR_ARG, "non-finite disorder");
+      m.hval[((size_t)c * N + i) * kHSlots] = w - mu;  // Hamiltonian.jl:18-22
+      for (size_t s = 0; s < hrow[i].size(); ++s)
+        m.hval[((size_t)c * N + i) * kHSlots + 1 + s] = hrow[i][s].second;
+      m.gersh = std::max(m.gersh, std::fabs(w - mu) + off);
+    }
+  }
+  // --- pairing pattern with the reference overwrite order (Hamiltonian.jl:68-83);
+  // both orientations of a bond are written together, so the map is symmetric
+  std::map<std::pair<int, int>, int> dmap;
+  for (int i = 0; i < N; ++i)
+    for (int dir = 0; dir < 2; ++dir) {
+      const int j = NN(i, dir);
+      const int src = i + N * dir;
+      dmap[{i, j}] = src;
+      dmap[{j, i}] = src;
+    }
+  m.Dcol.assign((size_t)N * kSlots, -1);
+  m.Dsrc.assign((size_t)N * kSlots, -1);
+  std::vector<int> dcount(N, 0);
+  for (auto& kv : dmap) {
+    const int r = kv.first.first;
+    if (dcount[r] >= kSlots) return fail(nullptr, DWH_ERR_ARG, "more than 4 pairing partners per site");
+    m.Dcol[(size_t)r * kSlots + dcount[r]] = kv.first.second;
+    m.Dsrc[(size_t)r * kSlots + dcount[r]] = kv.second;
+    dcount[r]++;
+  }
+  auto slot_of = [&](int r, int c) {
+    for (int s = 0; s < kSlots; ++s)
+      if (m.Dcol[(size_t)r * kSlots + s] == c) return s;
+    return -1;
+  };
+  m.bij.resize(2 * (size_t)N);
+  m.bji.resize(2 * (size_t)N);
+  for (int dir = 0; dir < 2; ++dir)
+    for (int i = 0; i < N; ++i) {
+      const int j = NN(i, dir);
+      const int sij = slot_of(i, j), sji = slot_of(j, i);
+      if (sij < 0 || sji < 0) return fail(nullptr, DWH_ERR_ARG, "bond missing from the pairing pattern");
+      m.bij[(size_t)dir * N + i] = i * kSlots + sij;
+      m.bji[(size_t)dir * N + i] = j * kSlots + sji;
+    }
+  // --- ‖h‖ <= min(Gershgorin, Lanczos bound), the latter only where certified
+  m.hmax = m.gersh;
+  if (lanczos)
+    m.hmax = h_norm_bound(hrow, disorder, mu, N, (int)Lx, (int)Ly, nchains, m.gersh, &m.lanczos, &m.certified);
+  // --- x-current operator (Observables.jl:237-283), duplicates summed
+  {
+    std::vector<std::map<int, double>> jrow(N);
+    m.tr_nbr.assign(3 * (size_t)N, 0);
+    for (int i = 0; i < N; ++i) {
+      const int js[3] = {NN(i, 0), NNN(i, 0), NNN(i, 3)};
+      const double ts[3] = {t, tp, tp};
+      for (int b = 0; b < 3; ++b) {
+        jrow[i][js[b]] += ts[b];
+        jrow[js[b]][i] -= ts[b];
+        m.tr_nbr[(size_t)b * N + i] = js[b];
+      }
+    }
+    m.tr_rowptr.assign(N + 1, 0);
+    for (int r = 0; r < N; ++r) {
+      for (auto& kv : jrow[r]) {
+        m.tr_col.push_back(kv.first);
+        m.tr_val.push_back(kv.second);
+      }
+      m.tr_rowptr[r + 1] = (int)m.tr_col.size();
+    }
+  }
+  m.site4.resize(4 * (size_t)N);
+  for (int i = 0; i < N; ++i)   // (i, +x), (i, +y), (i - x, +x), (i - y, +y): Delta index = site + N * (bond is +y)
+    for (int k = 0; k < 4; ++k) m.site4[4 * i + k] = (k < 2 ? i : NN(i, k)) + N * (k & 1);
+  return DWH_OK;
+}
+
 }  // namespace dwh
 
 using namespace dwh;
 
+// out: Gershgorin, Lanczos estimate, certified, the bound used, and whether
+// the band test accepts rho = 0 for the clean h (it must not)
 extern "C" int dwh_debug_h_bound(int64_t Lx, int64_t Ly, double t, double tp, double mu, const int64_t* nn_table,
                       const int64_t* nnn_table, int64_t nchains, const double* disorder, double* out) {
-  if (Lx < 1 || Ly < 1 || nchains < 1 || !nn_table || !nnn_table || !disorder || !out)
-    return fail(nullptr, DWH_ERR_ARG, "bad lattice / NULL argument");
-  const int64_t N64 = Lx * Ly;
-  if (N64 > 9216) return fail(nullptr, DWH_ERR_ARG, "N = Lx*Ly > 9216 not supported");
-  for (int64_t e = 0; e < 4 * N64; ++e)
-    if (nn_table[e] < 1 || nn_table[e] > N64 || nnn_table[e] < 1 || nnn_table[e] > N64)
-      return fail(nullptr, DWH_ERR_ARG, "neighbour table entry out of [1, N]");
-  const int N = (int)N64;
-  const auto hrow = build_hrow(N, t, tp, nn_table, nnn_table);
-  double gersh = 0;
-  for (int64_t c = 0; c < nchains; ++c)
-    for (int i = 0; i < N; ++i) {
-      double off = 0;
-      for (const auto& e : hrow[i]) off += std::fabs(e.second);
-      gersh = std::max(gersh, std::fabs(disorder[c * N64 + i] - mu) + off);
-    }
-  double lz = 0;
-  bool ok = false;
-  out[3] = h_norm_bound(hrow, disorder, mu, N, (int)Lx, (int)Ly, nchains, gersh, &lz, &ok);
-  out[0] = gersh;
-  out[1] = lz;
-  out[2] = ok ? 1.0 : 0.0;
-  out[4] = certify_spectral_bound(hrow, std::vector<double>(N, -mu).data(), N, (int)Lx, (int)Ly, 0.0) ? 1.0 : 0.0;
+  if (!out) return fail(nullptr, DWH_ERR_ARG, "NULL output");
+  HostModel m;
+  if (int rc = build_host_model(Lx, Ly, t, tp, mu, nn_table, nnn_table, nchains, disorder, &m)) return rc;
+  out[0] = m.gersh;
+  out[1] = m.lanczos;
+  out[2] = m.certified ? 1.0 : 0.0;
+  out[3] = m.hmax;
+  out[4] = certify_spectral_bound(m.hrow, std::vector<double>(m.N, -mu).data(), m.N, (int)Lx, (int)Ly, 0.0) ? 1.0 : 0.0;
   return DWH_OK;
 }

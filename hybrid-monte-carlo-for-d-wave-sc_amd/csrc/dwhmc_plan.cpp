@@ -1,7 +1,8 @@
 // The cyclic-reduction plan (dwhmc_plan.h): block cyclic reduction of the
 // periodic block-tridiagonal H_BdG - i y into launch stages, the sparse
 // level-0 patterns, the product stages' configuration and dispatch-ordered
-// slots, and the host-only dataflow check of a plan (dwh_debug_cr_plan_*).
+// slots — all behind plan_cr, which context creation and the host-only dataflow
+// check of a plan (dwh_debug_cr_plan_*) both call — and choose_algo.
 // Index arithmetic only — no device call, no vendor library:
 // tools/host_check/plan_main.cpp links this file and dwhmc_model.cpp alone.
 #include "dwhmc_plan.h"
@@ -13,6 +14,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <set>
+#include <string>
 #include <utility>
 
 #include "../../include/dwhmc.h"
@@ -157,12 +159,27 @@ int sp_nrow(const std::vector<int>& pat, int b, int r, int BP) {
 // (8 x 8: 4 blocks of two rows instead of 8 half-empty ones, one CR level
 // less).  Wider lattices keep one row per block: more rows would widen the
 // blocks, and at L = 16 two rows per block (BP 64) measured slower than one
-// (profiles/r04_exp_cr_two_row_blocks_C2.txt).
+// (profiles/r04_exp_cr_two_row_blocks_C2.txt).  0: not even one row fits a
+// supported block size.
 int cr_rows_per_block(int64_t Lx, int64_t Ly) {
   auto ok = [&](int64_t r) { return r >= 1 && Ly % r == 0 && dwh::cr_supported_bp((int)(2 * ((r * Lx + 15) / 16 * 16))); };
   int64_t r = std::max<int64_t>(1, 16 / Lx);
   while (r > 1 && !ok(r)) --r;
-  return (int)r;
+  return ok(r) ? (int)r : 0;
+}
+
+int choose_algo(int32_t algo_req, int64_t Lx, int64_t Ly, AlgoChoice* out) {
+  std::string want = "auto";
+  if (algo_req == DWH_ALGO_DENSE) want = "dense";
+  else if (algo_req == DWH_ALGO_CR) want = "cr";
+  else if (algo_req == DWH_ALGO_EIG) want = "eig";
+  else if (const char* e = std::getenv("DWHMC_ALGO")) want = e;
+  if (want != "auto" && want != "dense" && want != "cr" && want != "eig")
+    return fail(nullptr, DWH_ERR_ARG, "DWHMC_ALGO must be auto, dense, cr or eig");
+  out->want = want == "dense" ? DWH_ALGO_DENSE : want == "cr" ? DWH_ALGO_CR : want == "eig" ? DWH_ALGO_EIG : DWH_ALGO_AUTO;
+  out->cr_ok = cr_rows_per_block(Lx, Ly) > 0;
+  out->site_guard = out->want == DWH_ALGO_CR || (out->want == DWH_ALGO_AUTO && out->cr_ok);
+  return DWH_OK;
 }
 
 // Block cyclic reduction of the periodic block-tridiagonal H_BdG - i y (blocks
@@ -866,11 +883,7 @@ CrPlan build_cr_plan(int Lx, int Ly, int BP, const std::vector<int>& Dcol, bool 
 // DWHMC_CR_GEMM=TS:KSPLIT forces one
 // configuration for every stage (A/B runs; tests/test_gpu_parity.py runs
 // every compiled variant).
-CrGemmCfg cr_gemm_config(const CrDims& c, int ntasks, int maxt32, int maxt16, int ntmax, int ntiles16) {
-  (void)ntasks;
-  (void)maxt32;
-  (void)maxt16;
-  (void)ntmax;
+CrGemmCfg cr_gemm_config(const CrDims& c, int ntiles16) {
   // read at every context creation (tests switch it between contexts)
   const CrGemmCfg forced = [] {
     CrGemmCfg f{0, 1};
@@ -955,12 +968,51 @@ void cr_plan_dump(const CrPlan& pl, int64_t nbatch, bool cfg) {
   }
 }
 
+int plan_cr(int64_t Lx, int64_t Ly, int P, int nbatch, const std::vector<int>& Dcol, const std::vector<int>& hcol,
+            int side, int inv0, int ncu, CrDims* cd, CrPlan* plan) {
+  const int rows = cr_rows_per_block(Lx, Ly);
+  if (!rows) return fail(nullptr, DWH_ERR_ARG, "lattice row too wide for the CR path");
+  auto on = [](int arg, const char* name) {
+    if (arg != kCrFromEnv) return arg != 0;
+    const char* e = std::getenv(name);
+    return !(e && *e == '0');
+  };
+  CrDims& c = *cd;
+  c = CrDims{};
+  c.Lx = (int)Lx * rows;   // the CR lattice: `rows` lattice rows per block
+  c.Ly = (int)Ly / rows;
+  c.N = (int)(Lx * Ly);
+  c.BP = 2 * ((c.Lx + 15) / 16 * 16);   // top halves HP x BP, HP = c.Lx rounded to 16
+  c.P = P;
+  c.nbatch = nbatch;
+  c.inv32 = on(kCrFromEnv, "DWHMC_CR_INV32");
+  CrPlan& pl = *plan;
+  pl = build_cr_plan(c.Lx, c.Ly, c.BP, Dcol, dwh::cr_supported_side(c.BP) && on(side, "DWHMC_CR_SIDE"), nbatch, ncu,
+                     dwh::cr_supported_inv0(c.BP) && on(inv0, "DWHMC_CR_INV0"), &hcol);
+  c.nblk = pl.nblk;
+  c.item = (int64_t)c.nblk * (c.BP / 2) * c.BP;
+  if ((uint64_t)c.item >= (uint64_t)dwh::kCrNone)
+    return fail(nullptr, DWH_ERR_ARG, "CR pool: a batch item exceeds 2^32 elements (32-bit block-product offsets)");
+  pl.slots.clear();
+  for (CrStage& st : pl.stages) {
+    if (st.kind != 1) continue;
+    st.cfg = cr_gemm_config(c, st.ntiles);
+    if (st.cfg.ts != 16) continue;
+    st.nswg = cr_gemm_slot_wgs(c, st.ntiles, st.cfg);
+    st.sfirst = (int)pl.slots.size();
+    pl.slots.resize(pl.slots.size() + (size_t)st.nswg * (4 / st.cfg.ksplit));
+    cr_gemm_slots(c, pl.tiles16.data() + st.tfirst, st.ntiles, st.cfg, pl.slots.data() + st.sfirst);
+  }
+  return DWH_OK;
+}
+
 namespace {
-// hopping columns (kHSlots per site: the site, then its NN / NNN partners in
-// build_hrow's order) of a periodic Lx x Ly lattice with the reference's
-// tables (src/Types.jl:60-80): what dwh_create derives from ModelParameters
-std::vector<int> standard_hcol(int Lx, int Ly) {
-  const int N = Lx * Ly;
+// What dwh_create plans for a periodic Lx x Ly lattice with the reference's
+// tables (src/Types.jl:60-80) and NN pairing bonds, nbatch batch items
+int plan_periodic(int64_t Lx, int64_t Ly, int64_t nbatch, int32_t side, int32_t inv0, CrDims* c, CrPlan* pl) {
+  if (Lx < 1 || Ly < 1 || nbatch < 1) return fail(nullptr, DWH_ERR_ARG, "bad lattice / batch");
+  if (Lx > 9216 || Ly > 9216 || Lx * Ly > 9216) return fail(nullptr, DWH_ERR_ARG, "lattice larger than dwh_create takes");
+  const int N = (int)(Lx * Ly);
   std::vector<int64_t> nn((size_t)4 * N), nnn((size_t)4 * N);
   auto idx = [&](int x, int y) { return (int64_t)(((y % Ly + Ly) % Ly) * Lx + ((x % Lx + Lx) % Lx)) + 1; };
   for (int y = 0; y < Ly; ++y)
@@ -975,27 +1027,10 @@ std::vector<int> standard_hcol(int Lx, int Ly) {
       nnn[2 * N + i] = idx(x - 1, y - 1);
       nnn[3 * N + i] = idx(x + 1, y - 1);
     }
-  const auto hrow = build_hrow(N, 1.0, -0.35, nn.data(), nnn.data());
-  std::vector<int> hcol((size_t)N * kHSlots, -1);
-  for (int i = 0; i < N; ++i) {
-    hcol[(size_t)i * kHSlots] = i;
-    for (size_t k = 0; k < hrow[i].size() && k + 1 < (size_t)kHSlots; ++k) hcol[(size_t)i * kHSlots + 1 + k] = hrow[i][k].first;
-  }
-  return hcol;
-}
-
-// pairing columns (+x, +y, -x, -y) of every site of a periodic Lx x Ly lattice
-std::vector<int> nn_pairing_cols(int Lx, int Ly) {
-  const int N = Lx * Ly;
-  std::vector<int> Dcol((size_t)N * kSlots);
-  for (int i = 0; i < N; ++i) {
-    const int x = i % Lx, y = i / Lx;
-    Dcol[(size_t)i * kSlots + 0] = y * Lx + (x + 1) % Lx;
-    Dcol[(size_t)i * kSlots + 1] = ((y + 1) % Ly) * Lx + x;
-    Dcol[(size_t)i * kSlots + 2] = y * Lx + (x - 1 + Lx) % Lx;
-    Dcol[(size_t)i * kSlots + 3] = ((y - 1 + Ly) % Ly) * Lx + x;
-  }
-  return Dcol;
+  const std::vector<double> clean((size_t)N, 0.0);
+  HostModel m;
+  if (int rc = build_host_model(Lx, Ly, 1.0, -0.35, 0.0, nn.data(), nnn.data(), 1, clean.data(), &m, false)) return rc;
+  return plan_cr(Lx, Ly, 1, (int)nbatch, m.Dcol, m.hcol, side != 0, inv0 != 0, 256, c, pl);
 }
 }  // namespace
 
@@ -1014,15 +1049,10 @@ extern "C" {
 // accumulate input, no two tasks of a stage write the same block, and every
 // block the force / E_f gather reads was written.
 int dwh_debug_cr_plan_check(int64_t Lx, int64_t Ly, int64_t nbatch, int32_t side, int32_t inv0, int64_t* stats) {
-  if (Lx < 1 || Ly < 1 || nbatch < 1) return fail(nullptr, DWH_ERR_ARG, "bad lattice / batch");
-  std::vector<int> Dcol = nn_pairing_cols((int)Lx, (int)Ly);
-  if (!dwh::cr_supported_bp((int)(2 * ((Lx + 15) / 16 * 16))))
-    return fail(nullptr, DWH_ERR_ARG, "lattice row too wide for the CR path");
-  const int rows = cr_rows_per_block(Lx, Ly), Lxc = (int)Lx * rows, Lyc = (int)Ly / rows;
-  const int BP = 2 * ((Lxc + 15) / 16 * 16);
-  const std::vector<int> hcol = standard_hcol((int)Lx, (int)Ly);
-  const CrPlan pl = build_cr_plan(Lxc, Lyc, BP, Dcol, side && dwh::cr_supported_side(BP), (int)nbatch,
-                                  256, inv0 && dwh::cr_supported_inv0(BP), &hcol);
+  CrDims c;
+  CrPlan pl;
+  if (int rc = plan_periodic(Lx, Ly, nbatch, side, inv0, &c, &pl)) return rc;
+  const int Lyc = c.Ly, BP = c.BP;
   cr_plan_dump(pl, nbatch, false);
   std::vector<int> written(pl.nblk, -1);   // stage of the first write; -2: ready from the start
   for (int b = 0; b < 3 * Lyc && b < pl.nblk; ++b) written[b] = -2;
@@ -1149,15 +1179,11 @@ int dwh_debug_cr_plan_check(int64_t Lx, int64_t Ly, int64_t nbatch, int32_t side
 }
 
 int dwh_debug_cr_plan_flops(int64_t Lx, int64_t Ly, int64_t nbatch, int32_t side, int32_t inv0, double* flops) {
-  if (Lx < 1 || Ly < 1 || nbatch < 1 || !flops) return fail(nullptr, DWH_ERR_ARG, "bad lattice / batch / output");
-  if (!dwh::cr_supported_bp((int)(2 * ((Lx + 15) / 16 * 16))))
-    return fail(nullptr, DWH_ERR_ARG, "lattice row too wide for the CR path");
-  const int rows = cr_rows_per_block(Lx, Ly), Lxc = (int)Lx * rows, Lyc = (int)Ly / rows;
-  const int BP = 2 * ((Lxc + 15) / 16 * 16);
-  std::vector<int> Dcol = nn_pairing_cols((int)Lx, (int)Ly);
-  const std::vector<int> hcol = standard_hcol((int)Lx, (int)Ly);
-  const CrPlan pl = build_cr_plan(Lxc, Lyc, BP, Dcol, side && dwh::cr_supported_side(BP), (int)nbatch,
-                                  256, inv0 && dwh::cr_supported_inv0(BP), &hcol);
+  if (!flops) return fail(nullptr, DWH_ERR_ARG, "bad lattice / batch / output");
+  CrDims c;
+  CrPlan pl;
+  if (int rc = plan_periodic(Lx, Ly, nbatch, side, inv0, &c, &pl)) return rc;
+  const int BP = c.BP;
   const double bp3 = 8.0 * BP * (double)BP * BP;
   flops[0] = flops[1] = flops[2] = 0.0;
   for (const CrStage& st : pl.stages) {

@@ -1,7 +1,11 @@
-// The cyclic-reduction plan of the C-ABI context (dwhmc_plan.cpp): the stage
-// list build_cr_plan derives from the lattice, the sparse level-0 operand
-// arrays and the dispatch-ordered slots of the 16 x 16 product stages.  Pure
-// host index arithmetic: needs no device.  Not part of the public ABI.
+// The cyclic-reduction plan of the C-ABI context (dwhmc_plan.cpp): the choice
+// of algorithm and guard, and plan_cr, the one entry point that turns a
+// lattice into what the CR launches index by — block geometry, the stage list
+// build_cr_plan derives, the product stages' configurations and the
+// dispatch-ordered slots of the 16 x 16 stages — plus the sparse level-0
+// operand arrays.  Context creation and the host-only checks
+// (dwh_debug_cr_plan_*) go through the same plan_cr.  Pure host index
+// arithmetic: needs no device.  Not part of the public ABI.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -67,20 +71,32 @@ SpTaskArrays cr_sparse_task_arrays(const CrPlan& pl, int BP, const std::vector<d
 void cr_sparse_colvals(const std::vector<int>& colpat, int Lx, int Ly, int BP, const std::vector<int>& hcol,
                        const std::vector<double>& hval, const std::vector<int>& Dcol, const std::vector<int>& Dsrc,
                        std::vector<double2>& colval, std::vector<int>& colsrc);
-// lattice rows per CR block
+// lattice rows per CR block; 0: a lattice row does not fit a supported block
+// (2 Lx > 128), the CR path cannot run this lattice
 int cr_rows_per_block(int64_t Lx, int64_t Ly);
-// the plan of an Lx x Ly CR lattice of BP-wide blocks (dwhmc_plan.cpp)
-CrPlan build_cr_plan(int Lx, int Ly, int BP, const std::vector<int>& Dcol, bool side, int nbatch, int ncu, bool inv0,
-                     const std::vector<int>* hcol);
-// tile pairs of a stage (CrTile::pad1 = the second tile's column, -1 single), one per wave
-// maxt32 / maxt16: the largest cr_task_tiles over the stage's tasks at ts = 32 / 16;
-// ntmax: the largest term count
-CrGemmCfg cr_gemm_config(const CrDims& c, int ntasks, int maxt32, int maxt16, int ntmax, int ntiles16);
-// 16 x 16 stages (cfg.ts == 16): the dispatch-ordered slots of the stage's
-// (task, tile) list tl16 (ntl16 entries per batch item) over every batch item,
-// a whole number of workgroups (cr_gemm_slot_wgs of them)
-int cr_gemm_slot_wgs(const CrDims& c, int ntl16, const CrGemmCfg& cfg);
-void cr_gemm_slots(const CrDims& c, const CrTile* tl16, int ntl16, const CrGemmCfg& cfg, CrSlot* out);
+
+// Which path a context runs and which guard protects it.  want: algo_req, or
+// (DWH_ALGO_AUTO) DWHMC_ALGO = auto | dense | cr | eig.  auto runs cr when the
+// lattice fits a CR block (cr_ok), else dense, and eig when the pole selection
+// finds kappa beyond the table.  The site guard goes with the CR path (its
+// level-0 inversion launch checks it) unless the poles end on eig.
+struct AlgoChoice {
+  int32_t want = 0;   // DWH_ALGO_*
+  bool cr_ok = false, site_guard = false;
+};
+int choose_algo(int32_t algo_req, int64_t Lx, int64_t Ly, AlgoChoice* out);
+
+// The CR path's whole host side for an Lx x Ly lattice with P poles and nbatch
+// = chains x P batch items: the block geometry (*c), the stage list, each
+// product stage's configuration and the dispatch-ordered slots of the 16 x 16
+// stages.  side / inv0: side work on the inversion launches / level-0
+// inversions from the static R blocks, where the block size supports them;
+// kCrFromEnv: on unless DWHMC_CR_SIDE=0 / DWHMC_CR_INV0=0 (A/B runs, tests).
+// DWHMC_CR_INV32=0: BP = 32 inversions by k_cr_inv<2>.  DWH_ERR_ARG: a lattice
+// row too wide, or a batch item of 2^32 elements or more.
+constexpr int kCrFromEnv = -1;
+int plan_cr(int64_t Lx, int64_t Ly, int P, int nbatch, const std::vector<int>& Dcol, const std::vector<int>& hcol,
+            int side, int inv0, int ncu, CrDims* c, CrPlan* pl);
 // DWHMC_CR_PLAN_DUMP=1: one line per stage to stderr (nbatch inversion
 // workgroups per block; cfg: the product stages' configurations are chosen)
 void cr_plan_dump(const CrPlan& pl, int64_t nbatch, bool cfg);
