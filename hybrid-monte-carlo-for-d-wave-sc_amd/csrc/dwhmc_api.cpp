@@ -152,17 +152,14 @@ void cr_enqueue(dwh_ctx* ctx) {
       guard = dwh::SiteGuard{};
     } else if (st.kind == 2) {
       Scope s(ctx, T_CR_SPARSE, st.flops * c.nbatch);
-      const size_t spE = (size_t)dwh::kCrSpNZ * c.BP, spR = (size_t)dwh::kCrSpNZ * (c.BP / 2);
-      const SpTaskArrays& sa = ctx->sp_arr;
+      const size_t spE = (size_t)dwh::kCrSpNZ * c.BP, HP = (size_t)c.BP / 2;
       if (st.sp == 0)
-        dwh::launch_cr_sp_fwd(c, ctx->bpool, ctx->d_sp_fwd + st.first, st.n, ctx->d_sp_row + st.first * 3 * spR,
-                              ctx->d_sp_cv + st.first * 3 * spE, ctx->d_sp_cm + st.first * 3 * spE, ctx->Delta,
-                              ctx->stream);
+        dwh::launch_cr_sp_fwd(c, ctx->bpool, ctx->d_sp_rf + st.first * HP, st.n, ctx->d_sp_cv + st.first * 3 * spE,
+                              ctx->d_sp_cm + st.first * 3 * spE, ctx->Delta, ctx->stream);
       else
-        dwh::launch_cr_sp_bwd(c, ctx->bpool, ctx->d_sp_bwd + st.first, st.n,
-                              ctx->d_sp_row + sa.row_bwd0 + st.first * 2 * spR,
-                              ctx->d_sp_cv + sa.col_bwd0 + st.first * 2 * spE,
-                              ctx->d_sp_cm + sa.col_bwd0 + st.first * 2 * spE, ctx->Delta, ctx->stream);
+        dwh::launch_cr_sp_bwd(c, ctx->bpool, ctx->d_sp_rb + st.first * HP, st.n,
+                              ctx->d_sp_cv + ctx->sp_arr.col_bwd0 + st.first * 2 * spE,
+                              ctx->d_sp_cm + ctx->sp_arr.col_bwd0 + st.first * 2 * spE, ctx->Delta, ctx->stream);
     } else {
       Scope s(ctx, T_CR_GEMM, st.flops * c.nbatch);
       dwh::launch_cr_gemm(c, ctx->bpool, ctx->d_tasks + st.first, st.n, st.maxt32, st.maxt16,
@@ -342,15 +339,9 @@ int device_side(dwh_ctx* ctx) {
     ALLOC(bpool, (size_t)d.nbatch * ctx->cr.item);
     UPLOAD(d_tasks, pl.tasks);
     UPLOAD(d_slots, pl.slots);
-    UPLOAD(d_sp_fwd, pl.sp_fwd);
-    UPLOAD(d_sp_bwd, pl.sp_bwd);
-    if (!pl.colpat.empty()) {
-      std::vector<double2> colval;
-      std::vector<int> colsrc;
-      cr_sparse_colvals(pl.colpat, ctx->cr.Lx, ctx->cr.Ly, ctx->cr.BP, m.hcol, m.hval, m.Dcol, m.Dsrc, colval, colsrc);
-      ctx->sp_arr = cr_sparse_task_arrays(pl, ctx->cr.BP, colval, colsrc);
-    }
-    UPLOAD(d_sp_row, ctx->sp_arr.row);
+    ctx->sp_arr = cr_sparse_task_arrays(pl, ctx->cr.Lx, ctx->cr.Ly, ctx->cr.BP, m.hcol, m.hval, m.Dcol, m.Dsrc);
+    UPLOAD(d_sp_rf, ctx->sp_arr.rf);
+    UPLOAD(d_sp_rb, ctx->sp_arr.rb);
     UPLOAD(d_sp_cv, ctx->sp_arr.cv);
     UPLOAD(d_sp_cm, ctx->sp_arr.cm);
     ALLOC(efpart, 2 * (size_t)d.nbatch);

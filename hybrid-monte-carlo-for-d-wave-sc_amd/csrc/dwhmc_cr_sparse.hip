@@ -23,15 +23,20 @@
 //     T = -Dinv M, then G_ee = Dinv - T Dinv.
 //
 // Blocks are top halves (HP x BP) of M-form [[A, B], [conj B, -conj A]] or
-// Q-form [[A, B], [-conj B, conj A]] blocks (dwhmc_cr.hip); the sparse
-// operands are read through per-block patterns of the FULL BP x BP matrix
-// (rows and columns, kCrSpNZ entries each, built on the host from the hopping
-// and pairing tables exactly as k_cr_fill writes the blocks): entry = offset
-// of the stored top-half element | (column or row index) << 14 | op << 22,
-// op 0: the element, 1: its conjugate, 2: minus its conjugate (the
-// synthesised bottom half), 3: empty (reads element 0, weight zero, so every
-// load is unconditional and issued up front).  Pattern layout
-// [block][entry][BP] (lanes over the last index read contiguous words).
+// Q-form [[A, B], [-conj B, conj A]] blocks (dwhmc_cr.hip).  Everything about
+// the sparse operands except Δ is fixed at context creation, so the host
+// resolves it (dwhmc_plan.cpp):
+//   left operands (sparse . dense): one record per (task, output row)
+//   (CrSpRowFwd / CrSpRowBwd, dwhmc_internal.h) with the row's kCrSpNZ - 1
+//   hopping slots — static value, sign applied, and the offset of the dense
+//   operand's stored row — then its pairing slot — ±1/2, the Δ index and the
+//   stored row the synthesised bottom row comes from — and the task's own
+//   dense rows.  A wave reads it with a few wide scalar loads at an index
+//   that needs only the workgroup id; the Δ load of the pairing slots is the
+//   one dependent value before the dense element loads.  Which slot reads a
+//   stored row and which a synthesised one is fixed by the slot order.
+//   right operands (dense . sparse): per-task column arrays [operand][entry]
+//   [BP] of values and meta words, staged once per workgroup in LDS.
 // One wave per output row: every row of every output depends only on rows of
 // the inputs, and the backward M = L_a Z_a + U_e Z_c is formed as
 // Y_a U_a + Y_c L_e (the same sum regrouped), from the wave's own Y rows.
@@ -41,51 +46,49 @@
 namespace dwh {
 namespace {
 
-// stored value of pattern entry e (op 3: zero), times -1 when NEG, for a
-// wave-uniform entry: the op's signs and the zeroing act on the bit patterns
-// (scalar ALU; the value comes through a scalar load)
-template <bool NEG = false>
-__device__ __forceinline__ double2 sp_sval(const double2* __restrict__ S, int e) {
-  constexpr unsigned long long SB = 1ull << 63, N = NEG ? SB : 0ull;
-  const int off = e & 0x3fff, op = (e >> 22) & 3;
-  const double2 v = S[off];
-  const unsigned long long keep = op == 3 ? 0ull : ~0ull;
-  const unsigned long long bx = (__builtin_bit_cast(unsigned long long, v.x) ^ (op == 2 ? SB : 0ull) ^ N) & keep;
-  const unsigned long long by = (__builtin_bit_cast(unsigned long long, v.y) ^ (op == 1 ? SB : 0ull) ^ N) & keep;
-  return make_double2(__builtin_bit_cast(double, bx), __builtin_bit_cast(double, by));
-}
-__device__ __forceinline__ int sp_idx(int e) { return (e >> 14) & 0xff; }
-
 // a += b c
 __device__ __forceinline__ void cmac(double2& a, double2 b, double2 c) {
   a.x = fma(b.x, c.x, fma(-b.y, c.y, a.x));
   a.y = fma(b.x, c.y, fma(b.y, c.x, a.y));
+}
+// a += s c, s real
+__device__ __forceinline__ void rmac(double2& a, double s, double2 c) {
+  a.x = fma(s, c.x, a.x);
+  a.y = fma(s, c.y, a.y);
 }
 
 __device__ __forceinline__ double sp_flip(double x, unsigned m) {
   return __builtin_bit_cast(double, __builtin_bit_cast(unsigned long long, x) ^ ((unsigned long long)m << 32));
 }
 
-// Column c of the full BP x BP M-form block whose top half X (row-major
-// HP x BP) is stored, with its lane-constant parts precomputed: a row access
-// is one select for the column and two sign-bit XORs.  Bottom row HP + k,
-// column c: conj(X[k, c + HP]) (c < HP) or -conj(X[k, c - HP]) (c >= HP).
+// a wave-uniform double back in scalar registers
+__device__ __forceinline__ double sp_uniform(double x) {
+  const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
+  return __builtin_bit_cast(double, (unsigned long long)hi << 32 | lo);
+}
+
+// Column c of the synthesised bottom half of an M-form block whose top half
+// is stored: element (HP + k, c) = conj(X[k, c + HP]) (c < HP) or
+// -conj(X[k, c - HP]) (c >= HP) — one load at the rotated column and two
+// lane-constant sign-bit XORs.  Columns and rows as byte offsets.
 template <int BP>
-struct FullCol {
-  int c, crot;
-  unsigned mx, my;   // sign-bit masks of a synthesised entry's real / imaginary part
-  __device__ __forceinline__ explicit FullCol(int col) : c(col) {
-    constexpr int HP = BP / 2;
-    crot = c < HP ? c + HP : c - HP;
-    mx = c >= HP ? 0x80000000u : 0u;
-    my = c < HP ? 0x80000000u : 0u;
+struct BotCol {
+  unsigned crot;
+  unsigned mx, my;   // sign-bit masks of the real / imaginary part
+  __device__ __forceinline__ explicit BotCol(unsigned cb) {
+    constexpr unsigned HB = BP / 2 * sizeof(double2);
+    crot = cb < HB ? cb + HB : cb - HB;
+    mx = cb >= HB ? 0x80000000u : 0u;
+    my = cb < HB ? 0x80000000u : 0u;
   }
-  // element (kk, c), kk wave-uniform
-  __device__ __forceinline__ double2 at(const double2* __restrict__ X, int kk) const {
-    constexpr int HP = BP / 2;
-    const bool top = kk < HP;
-    const double2 u = X[(top ? kk : kk - HP) * BP + (top ? c : crot)];
-    return make_double2(sp_flip(u.x, top ? 0u : mx), sp_flip(u.y, top ? 0u : my));
+  // the stored element behind it: row = the stored row k of a pool block,
+  // from the batch item's base; sign() then makes it the synthesised one
+  __device__ __forceinline__ double2 ld(const double2* base, unsigned row) const {
+    return *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(base) + (row + crot));
+  }
+  __device__ __forceinline__ double2 sign(double2 u) const {
+    return make_double2(sp_flip(u.x, mx), sp_flip(u.y, my));
   }
 };
 
@@ -99,17 +102,24 @@ __device__ __forceinline__ double2 sp_cval(double2 x, int m) {
   return make_double2(op == 2 ? -0.5 * x.x : 0.5 * x.x, op == 0 ? 0.5 * x.y : -0.5 * x.y);   // op 1: conj, 2: -conj
 }
 
-constexpr int kSpRowsWG = 4;   // one output row per wave, four waves per workgroup
-constexpr int NZ = kCrSpNZ;
-// waves per SIMD the register budget is sized for at BP <= 64 (forward,
-// backward): six (<= 80 VGPRs, 79 used) and five (<= 96), the most without
-// scratch spills, so the C3 forward stage (1536 workgroups of 25 KB LDS) is
-// resident in one round (-DSP_WAVES_F / -DSP_WAVES_B for A/B builds)
+constexpr int kSpRowsWG = 4;   // one output row per wave at a time, four waves per workgroup
+constexpr int NZ = kCrSpNZ, NH = kCrSpNZ - 1;   // slots per row: NH hopping, then the pairing slot
+// waves per SIMD the register budget is sized for at BP <= 64: six (<= 80
+// VGPRs) for both stages, so the C3 stages (1536 workgroups of 25.5 / 25 KB
+// LDS, six per CU) are resident in one round (-DSP_WAVES_F / -DSP_WAVES_B
+// for A/B builds)
 #ifndef SP_WAVES_F
 #define SP_WAVES_F 6
 #endif
 #ifndef SP_WAVES_B
-#define SP_WAVES_B 5
+#define SP_WAVES_B 6
+#endif
+// output rows a backward wave takes in turn (its workgroup stages the column
+// data once for all of them).  One: two rows (-DSP_RPW_B=2), at five or six
+// waves, and five waves with one row all measured slower
+// (profiles/sparse_records_ab.txt)
+#ifndef SP_RPW_B
+#define SP_RPW_B 1
 #endif
 template <int BP>
 constexpr int kSpWavesF = BP <= 64 ? SP_WAVES_F : 2;
@@ -122,272 +132,332 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Column data of the sparse right operands (dense . sparse products): every
-// output row of a workgroup uses the same column patterns, so the workgroup
-// stages them once in LDS — the value and the row index of each entry — from
-// the task's own column arrays (tcm / tcv: [NB][kCrSpNZ][BP], coalesced, no
-// dependence on the task descriptor), one load per entry behind the meta word.
-template <int BP, int NB>
-__device__ __forceinline__ void stage_columns(double2 (*cv)[kCrSpNZ][BP], unsigned char (*ci)[kCrSpNZ][BP],
-                                              const double2* __restrict__ tcv, const int* __restrict__ tcm,
-                                              const double2* __restrict__ Dc) {
-  constexpr int TOT = NB * NZ * BP, IT = (TOT + 64 * kSpRowsWG - 1) / (64 * kSpRowsWG);
-  int m[IT];
-#pragma unroll
-  for (int i = 0; i < IT; ++i) m[i] = tcm[min((int)threadIdx.x + 64 * kSpRowsWG * i, TOT - 1)];
-  double2 x[IT];
-#pragma unroll
-  for (int i = 0; i < IT; ++i) {   // one load per entry: the static value or Δ
-    const int q = min((int)threadIdx.x + 64 * kSpRowsWG * i, TOT - 1), s = m[i] & 0x3fffff;
-    x[i] = *(s ? Dc + (s - 1) : tcv + q);
-  }
-#pragma unroll
-  for (int i = 0; i < IT; ++i) {
-    const int q = threadIdx.x + 64 * kSpRowsWG * i;
-    if (q < TOT) {
-      (&cv[0][0][0])[q] = sp_cval(x[i], m[i]);
-      (&ci[0][0][0])[q] = (unsigned char)((unsigned)m[i] >> 24);
-    }
-  }
+// element at byte offset off (32 bits: a uniform base plus one offset
+// register per load) of a batch item's pool / of a staged LDS row
+__device__ __forceinline__ double2 sp_ld(const double2* base, unsigned off) {
+  return *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(base) + off);
+}
+__device__ __forceinline__ void sp_st(double2* base, unsigned off, double2 v) {
+  *reinterpret_cast<double2*>(reinterpret_cast<char*>(base) + off) = v;
 }
 
-// forward: one wave per output row r of the kept row k's D', U', L'; the
-// row's operands are loaded into registers up front (pattern words through
-// lanes, then every value and dense element at once), the V rows meet in LDS.
-template <int BP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesF<BP>))) void k_cr_sp_fwd(double2* __restrict__ pool, int64_t item,
-                                                   const CrSpFwd* __restrict__ tasks, const int* __restrict__ trow,
-                                                   const double2* __restrict__ tcv, const int* __restrict__ tcm,
-                                                   const double2* __restrict__ Delta, int twoN, int P, int nrb) {
-  constexpr int HP = BP / 2, NCL = (BP + 63) / 64;
-  constexpr int64_t BB = (int64_t)HP * BP;
-  constexpr int TA = 3 * NZ * BP, TR = 3 * NZ * HP;   // per-task column / row array sizes
-  __shared__ double2 cv[3][NZ][BP];
-  __shared__ unsigned char ci[3][NZ][BP];
-  __shared__ double2 sc[kSpRowsWG][3][BP];
-  const double2* Dc = Delta + (int64_t)(__builtin_amdgcn_readfirstlane(xcd_grid2d().y) / P) * twoN;
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int2 xy = xcd_grid2d();   // batch items grouped per XCD
-  const int ti = __builtin_amdgcn_readfirstlane(xy.x / nrb);
-  const int r = __builtin_amdgcn_readfirstlane((xy.x - ti * nrb) * kSpRowsWG + w);
-  const CrSpFwd t = tasks[ti];
-  double2* base = pool + (int64_t)xy.y * item;
-  const double2 *Dir = base + t.dir * BB, *Dil = base + t.dil * BB, *Dk = base + t.dk * BB;
-  int cl[NCL];
+// Column data of the sparse right operands (dense . sparse products): every
+// output row of a workgroup uses the same column patterns, so the workgroup
+// stages them once in LDS — the value of each entry and the LDS byte offset
+// of its row's element in a staged double2 row — from the task's own column
+// arrays (tcm / tcv: [NB][kCrSpNZ][BP], coalesced).  Three steps, so the meta
+// words are the kernel's first loads and the values (one load per entry
+// behind its meta word: the static value or Δ) follow the dense loads.
+template <int BP, int NB>
+struct ColStage {
+  static constexpr int TOT = NB * NZ * BP, IT = (TOT + 64 * kSpRowsWG - 1) / (64 * kSpRowsWG);
+  int m[IT];
+  double2 x[IT];
+  __device__ __forceinline__ void load_meta(const int* __restrict__ tcm) {
 #pragma unroll
-  for (int j = 0; j < NCL; ++j) cl[j] = min(l + 64 * j, BP - 1);
-  // row r of U_k, L_er, L_el: pattern words and values are wave-uniform
-  // (scalar loads), negated here so the V rows come out with their sign
-  const int* rw = trow + (int64_t)ti * TR + r * 3 * NZ;
-  int pu[NZ], pr[NZ], pl[NZ];
-#pragma unroll
-  for (int e = 0; e < NZ; ++e) {
-    pu[e] = rw[e];
-    pr[e] = rw[NZ + e];
-    pl[e] = rw[2 * NZ + e];
+    for (int i = 0; i < IT; ++i) m[i] = tcm[min((int)threadIdx.x + 64 * kSpRowsWG * i, TOT - 1)];
   }
-  double2 wu[NZ], wr[NZ], wl[NZ];
+  __device__ __forceinline__ void load_values(const double2* __restrict__ tcv, const double2* __restrict__ Dc) {
 #pragma unroll
-  for (int e = 0; e < NZ; ++e) {
-    wu[e] = sp_sval<true>(base + t.uk * BB, pu[e]);
-    wr[e] = sp_sval<true>(base + t.ler * BB, pr[e]);
-    wl[e] = sp_sval<true>(base + t.lel * BB, pl[e]);
-  }
-  double2 dk[NCL];
-#pragma unroll
-  for (int j = 0; j < NCL; ++j) dk[j] = Dk[r * BP + cl[j]];
-  double2 xu[NZ][NCL], xr[NZ][NCL], xl[NZ][NCL];
-#pragma unroll
-  for (int j = 0; j < NCL; ++j) {
-    const FullCol<BP> fc(cl[j]);
-#pragma unroll
-    for (int e = 0; e < NZ; ++e) {
-      xu[e][j] = fc.at(Dir, sp_idx(pu[e]));
-      xr[e][j] = fc.at(Dir, sp_idx(pr[e]));
-      xl[e][j] = fc.at(Dil, sp_idx(pl[e]));
+    for (int i = 0; i < IT; ++i) {
+      const int q = min((int)threadIdx.x + 64 * kSpRowsWG * i, TOT - 1), s = m[i] & 0x3fffff;
+      x[i] = *(s ? Dc + (s - 1) : tcv + q);
     }
   }
-  stage_columns<BP, 3>(cv, ci, tcv + (int64_t)ti * TA, tcm + (int64_t)ti * TA, Dc);
+  // the meta words have arrived, and are not looked at before this point
+  __device__ __forceinline__ void pin_meta() {
+#pragma unroll
+    for (int i = 0; i < IT; ++i) asm volatile("" : "+v"(m[i]));
+  }
+  // The same with no value registers (backward stage): the raw values land
+  // in cv directly (asynchronous global -> LDS loads; the 64 entries of a
+  // wave's load are contiguous) and what is left of each meta word waits in
+  // ci (the row's byte offset, a multiple of 16, | 4 for a pairing entry |
+  // op), so nothing is held in registers while the loads are in flight.
+  // Once they have landed finish() applies it to the lane's own entries.
+  __device__ __forceinline__ void dma_values(double2 (*cv)[kCrSpNZ][BP], unsigned short (*ci)[kCrSpNZ][BP],
+                                             const double2* __restrict__ tcv, const double2* __restrict__ Dc) const {
+    static_assert(TOT % 64 == 0, "a wave's entries are all inside the arrays or all outside");
+    // (pin_meta() comes first: a wait for a meta word behind a load into LDS
+    // in flight would wait for that load, and all before it, as well)
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int q = (int)threadIdx.x + 64 * kSpRowsWG * i, s = m[i] & 0x3fffff;
+      const int q0 = __builtin_amdgcn_readfirstlane(((int)threadIdx.x & ~63) + 64 * kSpRowsWG * i);
+      if (TOT % (64 * kSpRowsWG) != 0 && q0 >= TOT) continue;
+      (&ci[0][0][0])[q] = (unsigned short)((((unsigned)m[i] >> 20) & 0xff0u) | (s ? 4u : 0u) | (((unsigned)m[i] >> 22) & 3u));
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s ? Dc + (s - 1) : tcv + q),
+                                       (__attribute__((address_space(3))) void*)(&cv[0][0][0] + q0), 16, 0, 0);
+    }
+  }
+  __device__ __forceinline__ static void finish(double2 (*cv)[kCrSpNZ][BP], unsigned short (*ci)[kCrSpNZ][BP]) {
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int q = threadIdx.x + 64 * kSpRowsWG * i;
+      if (q < TOT) {
+        const unsigned k = (&ci[0][0][0])[q];
+        // the meta word's Δ-index and op fields as sp_cval reads them
+        (&cv[0][0][0])[q] = sp_cval((&cv[0][0][0])[q], (int)((k >> 2 & 1u) | (k & 3u) << 22));
+        (&ci[0][0][0])[q] = (unsigned short)(k & 0xff0u);
+      }
+    }
+  }
+  __device__ __forceinline__ void store(double2 (*cv)[kCrSpNZ][BP], unsigned short (*ci)[kCrSpNZ][BP]) const {
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int q = threadIdx.x + 64 * kSpRowsWG * i;
+      if (q < TOT) {
+        (&cv[0][0][0])[q] = sp_cval(x[i], m[i]);
+        (&ci[0][0][0])[q] = (unsigned short)(((unsigned)m[i] >> 20) & 0xff0u);   // row * sizeof(double2)
+      }
+    }
+  }
+};
+
+// forward: one wave per output row r of the kept row k's D', U', L'.  The
+// record load is followed by the Δ load of the three pairing slots and every
+// dense element load at once; the V rows meet in LDS.
+template <int BP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesF<BP>))) void k_cr_sp_fwd(
+    double2* __restrict__ pool, int64_t item, const CrSpRowFwd* __restrict__ recs, const double2* __restrict__ tcv,
+    const int* __restrict__ tcm, const double2* __restrict__ Delta, int twoN, int P) {
+  constexpr int HP = BP / 2, NCL = (BP + 63) / 64, NRB = HP / kSpRowsWG;
+  constexpr int TA = 3 * NZ * BP;   // per-task column array size
+  __shared__ double2 cv[3][NZ][BP];
+  __shared__ unsigned short ci[3][NZ][BP];
+  __shared__ double2 sc[kSpRowsWG][3][BP];
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int2 xy = xcd_grid2d();   // batch items grouped per XCD; x = task * NRB + row block
+  const CrSpRowFwd t = recs[__builtin_amdgcn_readfirstlane(xy.x * kSpRowsWG + w)];
+  ColStage<BP, 3> cs;
+  cs.load_meta(tcm + (int64_t)(xy.x / NRB) * TA);
+  const double2* Dc = Delta + (int64_t)(xy.y / P) * twoN;
+  double2* base = pool + (int64_t)xy.y * item;
+  unsigned cl[NCL];   // this lane's columns, as byte offsets within a row
+#pragma unroll
+  for (int j = 0; j < NCL; ++j) cl[j] = min(l + 64 * j, BP - 1) * (unsigned)sizeof(double2);
+  // pairing entries of row r of -U_k, -L_er, -L_el: ∓Δ/2 (wave-uniform)
+  double2 pw[3];
+#pragma unroll
+  for (int o = 0; o < 3; ++o) {
+    const double2 d = Dc[t.pd[o]];
+    pw[o] = make_double2(sp_uniform(t.ps[o] * d.x), sp_uniform(t.ps[o] * d.y));
+  }
+  double2 dk[NCL], xh[3][NH][NCL], xp[3][NCL];
+#pragma unroll
+  for (int j = 0; j < NCL; ++j) {
+    const BotCol<BP> bc(cl[j]);
+    dk[j] = sp_ld(base, t.dk + cl[j]);
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+#pragma unroll
+      for (int e = 0; e < NH; ++e) xh[o][e][j] = sp_ld(base, t.ho[o][e] + cl[j]);
+      xp[o][j] = bc.ld(base, t.po[o]);
+    }
+  }
+  cs.load_values(tcv + (int64_t)(xy.x / NRB) * TA, Dc);
   // V1r = -U_k Dinv_er, V2r = -L_er Dinv_er, V2l = -L_el Dinv_el
 #pragma unroll
   for (int j = 0; j < NCL; ++j) {
-    double2 v1 = make_double2(0.0, 0.0), v2r = v1, v2l = v1;
+    const BotCol<BP> bc(cl[j]);
 #pragma unroll
-    for (int e = 0; e < NZ; ++e) {
-      cmac(v1, wu[e], xu[e][j]);
-      cmac(v2r, wr[e], xr[e][j]);
-      cmac(v2l, wl[e], xl[e][j]);
-    }
-    if (l + 64 * j < BP) {
-      sc[w][0][cl[j]] = v1;
-      sc[w][1][cl[j]] = v2r;
-      sc[w][2][cl[j]] = v2l;
+    for (int o = 0; o < 3; ++o) {
+      double2 v = make_double2(0.0, 0.0);
+#pragma unroll
+      for (int e = 0; e < NH; ++e) rmac(v, t.hv[o][e], xh[o][e][j]);
+      cmac(v, pw[o], bc.sign(xp[o][j]));
+      if (l + 64 * j < BP) sp_st(sc[w][o], cl[j], v);
     }
   }
+  cs.store(cv, ci);
   __syncthreads();
   // D'_k = D_k + V1r L_k + V2l U_el, U'_k = V1r U_er, L'_k = V2r L_k
-  double2 *On = base + t.od * BB, *Ou = base + t.ou * BB, *Ol = base + t.ol * BB;
 #pragma unroll
   for (int j = 0; j < NCL; ++j) {
-    const int c = cl[j];
+    const int c = cl[j] / sizeof(double2);
     double2 d = dk[j], u = make_double2(0.0, 0.0), lo = make_double2(0.0, 0.0);
 #pragma unroll
     for (int e = 0; e < NZ; ++e) {
       const double2 vl = cv[0][e][c], vu = cv[1][e][c], vr = cv[2][e][c];
-      const int kl = ci[0][e][c], ku = ci[1][e][c], kr = ci[2][e][c];
-      cmac(d, sc[w][0][kl], vl);
-      cmac(lo, sc[w][1][kl], vl);
-      cmac(d, sc[w][2][ku], vu);
-      cmac(u, sc[w][0][kr], vr);
+      const unsigned kl = ci[0][e][c], ku = ci[1][e][c], kr = ci[2][e][c];
+      cmac(d, sp_ld(sc[w][0], kl), vl);
+      cmac(lo, sp_ld(sc[w][1], kl), vl);
+      cmac(d, sp_ld(sc[w][2], ku), vu);
+      cmac(u, sp_ld(sc[w][0], kr), vr);
     }
     if (l + 64 * j < BP) {
-      On[r * BP + c] = d;
-      Ou[r * BP + c] = u;
-      Ol[r * BP + c] = lo;
+      sp_st(base, t.od + cl[j], d);
+      sp_st(base, t.ou + cl[j], u);
+      sp_st(base, t.ol + cl[j], lo);
     }
   }
 }
 
 // backward: one wave per output row r of the eliminated row e's Z_a, Z_c,
-// Y_a, Y_c and M = Y_a U_a + Y_c L_e.  Row r of each G block is staged in the
-// wave's LDS (Z gathers from it), full rows of the G blocks feed Y.
-template <int BP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesB<BP>))) void k_cr_sp_bwd(double2* __restrict__ pool, int64_t item,
-                                                   const CrSpBwd* __restrict__ tasks, const int* __restrict__ trow,
-                                                   const double2* __restrict__ tcv, const int* __restrict__ tcm,
-                                                   const double2* __restrict__ Delta, int twoN, int P, int nrb) {
-  constexpr int HP = BP / 2, NCL = (BP + 63) / 64;
-  constexpr int64_t BB = (int64_t)HP * BP;
-  constexpr int TA = 2 * NZ * BP, TR = 2 * NZ * HP;   // per-task column / row array sizes
+// Y_a, Y_c and M = Y_a U_a + Y_c L_e (RPW rows in turn).  Row r of each G
+// block is staged in the wave's LDS (Z gathers from it), full rows of the G
+// blocks feed Y.
+template <int BP, int RPW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesB<BP>))) void k_cr_sp_bwd(
+    double2* __restrict__ pool, int64_t item, const CrSpRowBwd* __restrict__ recs, const double2* __restrict__ tcv,
+    const int* __restrict__ tcm, const double2* __restrict__ Delta, int twoN, int P) {
+  constexpr int HP = BP / 2, NCL = (BP + 63) / 64, NRB = HP / (kSpRowsWG * RPW);
+  constexpr int TA = 2 * NZ * BP;   // per-task column array size
+  static_assert(HP % (kSpRowsWG * RPW) == 0, "row blocks tile the top half");
   __shared__ double2 cv[2][NZ][BP];
-  __shared__ unsigned char ci[2][NZ][BP];
+  __shared__ unsigned short ci[2][NZ][BP];
   __shared__ double2 gr[kSpRowsWG][4][BP];
   double2(*sc)[4][BP] = gr;   // the Y rows (sc[w][0 / 1]) reuse the wave's G rows once Z is formed
-  const double2* Dc = Delta + (int64_t)(__builtin_amdgcn_readfirstlane(xcd_grid2d().y) / P) * twoN;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int2 xy = xcd_grid2d();   // batch items grouped per XCD
-  const int ti = __builtin_amdgcn_readfirstlane(xy.x / nrb);
-  const int r = __builtin_amdgcn_readfirstlane((xy.x - ti * nrb) * kSpRowsWG + w);
-  const CrSpBwd t = tasks[ti];
+  const int2 xy = xcd_grid2d();   // batch items grouped per XCD; x = task * NRB + row block
+  ColStage<BP, 2> cs;
+  cs.load_meta(tcm + (int64_t)(xy.x / NRB) * TA);
+  const double2* Dc = Delta + (int64_t)(xy.y / P) * twoN;
   double2* base = pool + (int64_t)xy.y * item;
-  const double2 *Gaa = base + t.gaa * BB, *Gac = base + t.gac * BB, *Gca = base + t.gca * BB,
-                *Gcc = base + t.gcc * BB;
-  int cl[NCL];
+  unsigned cl[NCL];   // this lane's columns, as byte offsets within a row
 #pragma unroll
-  for (int j = 0; j < NCL; ++j) cl[j] = min(l + 64 * j, BP - 1);
-  // row r of L_a, U_e: wave-uniform pattern words and values (scalar loads)
-  const int* rw = trow + (int64_t)ti * TR + r * 2 * NZ;
-  int pa[NZ], pe[NZ];
+  for (int j = 0; j < NCL; ++j) cl[j] = min(l + 64 * j, BP - 1) * (unsigned)sizeof(double2);
+#pragma unroll 1
+  for (int i = 0; i < RPW; ++i) {
+    const CrSpRowBwd t = recs[__builtin_amdgcn_readfirstlane((xy.x * RPW + i) * kSpRowsWG + w)];
+    // pairing entries of row r of L_a, U_e: Δ/2 (wave-uniform)
+    double2 pw[2];
 #pragma unroll
-  for (int e = 0; e < NZ; ++e) {
-    pa[e] = rw[e];
-    pe[e] = rw[NZ + e];
-  }
-  double2 va[NZ], ve[NZ];
-#pragma unroll
-  for (int e = 0; e < NZ; ++e) {
-    va[e] = sp_sval(base + t.la * BB, pa[e]);
-    ve[e] = sp_sval(base + t.ue * BB, pe[e]);
-  }
-  // rows r of the G blocks (for Z) into this wave's LDS
-#pragma unroll
-  for (int j = 0; j < NCL; ++j)
-    if (l + 64 * j < BP) {
-      gr[w][0][cl[j]] = Gaa[r * BP + cl[j]];
-      gr[w][1][cl[j]] = Gca[r * BP + cl[j]];
-      gr[w][2][cl[j]] = Gac[r * BP + cl[j]];
-      gr[w][3][cl[j]] = Gcc[r * BP + cl[j]];
+    for (int o = 0; o < 2; ++o) {
+      const double2 d = Dc[t.pd[o]];
+      pw[o] = make_double2(sp_uniform(t.ps[o] * d.x), sp_uniform(t.ps[o] * d.y));
     }
-  double2 gaa[NZ][NCL], gac[NZ][NCL], gca[NZ][NCL], gcc[NZ][NCL];
+    // What Z needs goes straight into LDS (asynchronous global -> LDS loads,
+    // no registers, so the six-wave budget holds both operands' rows without
+    // scratch): the column data and row r of the G blocks (lane l's 16 bytes
+    // land at the row's base + 16 l, the row's own layout).  They go first:
+    // the meta words, loaded alongside the record, are here when it is, and
+    // their decode is out of the way before the rows fill the registers.
+    // (The order is pinned: left to itself the compiler moves the decode
+    // among the dense loads and sinks the Y sums below the barriers, which
+    // keeps every loaded row live across them, and spills.)
+    cs.pin_meta();
+    if (i == 0) cs.dma_values(cv, ci, tcv + (int64_t)(xy.x / NRB) * TA, Dc);
 #pragma unroll
-  for (int j = 0; j < NCL; ++j) {
-    const FullCol<BP> fc(cl[j]);
+    for (int j = 0; j < NCL; ++j)
+      if (l + 64 * j < BP) {
 #pragma unroll
-    for (int e = 0; e < NZ; ++e) {
-      gaa[e][j] = fc.at(Gaa, sp_idx(pa[e]));
-      gac[e][j] = fc.at(Gac, sp_idx(pa[e]));
-      gca[e][j] = fc.at(Gca, sp_idx(pe[e]));
-      gcc[e][j] = fc.at(Gcc, sp_idx(pe[e]));
+        for (int g = 0; g < 4; ++g)
+          __builtin_amdgcn_global_load_lds(
+              (const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(base) + (t.g[g] + cl[j])),
+              (__attribute__((address_space(3))) void*)&gr[w][g][64 * j], 16, 0, 0);
+      }
+    __builtin_amdgcn_sched_barrier(0);
+    // [operand L_a / U_e][G_aa, G_ac / G_ca, G_cc]
+    double2 gh[2][2][NH][NCL], gp[2][2][NCL];
+#pragma unroll
+    for (int j = 0; j < NCL; ++j) {
+      const BotCol<BP> bc(cl[j]);
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+#pragma unroll
+          for (int e = 0; e < NH; ++e) gh[o][g][e][j] = sp_ld(base, t.ho[o][g][e] + cl[j]);
+          gp[o][g][j] = bc.ld(base, t.po[o][g]);
+        }
     }
-  }
-  stage_columns<BP, 2>(cv, ci, tcv + (int64_t)ti * TA, tcm + (int64_t)ti * TA, Dc);
-  __syncthreads();
-  double2 *Oza = base + t.oza * BB, *Ozc = base + t.ozc * BB, *Oya = base + t.oya * BB,
-          *Oyc = base + t.oyc * BB, *Omx = base + t.omx * BB;
-  double2 yk[NCL][2];
-#pragma unroll
-  for (int j = 0; j < NCL; ++j) {
-    const int c = cl[j];
+    __builtin_amdgcn_sched_barrier(0);
     // Y_a[r, :] = L_a[r, :] G_aa + U_e[r, :] G_ca, Y_c[r, :] = L_a[r, :] G_ac + U_e[r, :] G_cc
+    double2 yk[NCL][2];
+#pragma unroll
+    for (int j = 0; j < NCL; ++j) {
+      const BotCol<BP> bc(cl[j]);
+      double2 ya = make_double2(0.0, 0.0), yc = ya;
+#pragma unroll
+      for (int o = 0; o < 2; ++o) {
+#pragma unroll
+        for (int e = 0; e < NH; ++e) {
+          rmac(ya, t.hv[o][e], gh[o][0][e][j]);
+          rmac(yc, t.hv[o][e], gh[o][1][e][j]);
+        }
+        cmac(ya, pw[o], bc.sign(gp[o][0][j]));
+        cmac(yc, pw[o], bc.sign(gp[o][1][j]));
+      }
+      yk[j][0] = ya;
+      yk[j][1] = yc;
+    }
+#pragma unroll
+    for (int j = 0; j < NCL; ++j)
+      asm volatile("" : "+v"(yk[j][0].x), "+v"(yk[j][0].y), "+v"(yk[j][1].x), "+v"(yk[j][1].y));
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();   // every wave's loads into LDS have landed
+    if (i == 0) {
+      cs.finish(cv, ci);
+      __syncthreads();
+    }
     // Z_a[r, :] = G_aa[r, :] U_a + G_ac[r, :] L_e, Z_c[r, :] = G_ca[r, :] U_a + G_cc[r, :] L_e
-    double2 ya = make_double2(0.0, 0.0), yc = ya, za = ya, zc = ya;
 #pragma unroll
-    for (int e = 0; e < NZ; ++e) {
-      cmac(ya, va[e], gaa[e][j]);
-      cmac(yc, va[e], gac[e][j]);
-      cmac(ya, ve[e], gca[e][j]);
-      cmac(yc, ve[e], gcc[e][j]);
-      const double2 wa = cv[0][e][c], we = cv[1][e][c];
-      const int ka = ci[0][e][c], ke = ci[1][e][c];
-      cmac(za, gr[w][0][ka], wa);
-      cmac(zc, gr[w][1][ka], wa);
-      cmac(za, gr[w][2][ke], we);
-      cmac(zc, gr[w][3][ke], we);
-    }
-    if (l + 64 * j < BP) {
-      Oya[r * BP + c] = ya;
-      Oyc[r * BP + c] = yc;
-      Oza[r * BP + c] = za;
-      Ozc[r * BP + c] = zc;
-    }
-    yk[j][0] = ya;
-    yk[j][1] = yc;
-  }
-  wave_sync();   // every lane's Z gathers from gr[w] are done
+    for (int j = 0; j < NCL; ++j) {
+      const int c = cl[j] / sizeof(double2);
+      double2 za = make_double2(0.0, 0.0), zc = za;
 #pragma unroll
-  for (int j = 0; j < NCL; ++j)
-    if (l + 64 * j < BP) {
-      sc[w][0][cl[j]] = yk[j][0];
-      sc[w][1][cl[j]] = yk[j][1];
+      for (int e = 0; e < NZ; ++e) {
+        const double2 wa = cv[0][e][c], we = cv[1][e][c];
+        const unsigned ka = ci[0][e][c], ke = ci[1][e][c];
+        cmac(za, sp_ld(gr[w][0], ka), wa);
+        cmac(zc, sp_ld(gr[w][1], ka), wa);
+        cmac(za, sp_ld(gr[w][2], ke), we);
+        cmac(zc, sp_ld(gr[w][3], ke), we);
+      }
+      if (l + 64 * j < BP) {
+        sp_st(base, t.oya + cl[j], yk[j][0]);
+        sp_st(base, t.oyc + cl[j], yk[j][1]);
+        sp_st(base, t.oza + cl[j], za);
+        sp_st(base, t.ozc + cl[j], zc);
+      }
     }
-  wave_sync();
-  // M[r, :] = Y_a[r, :] U_a + Y_c[r, :] L_e
+    wave_sync();   // every lane's Z gathers from gr[w] are done
 #pragma unroll
-  for (int j = 0; j < NCL; ++j) {
-    const int c = cl[j];
-    double2 mx = make_double2(0.0, 0.0);
+    for (int j = 0; j < NCL; ++j)
+      if (l + 64 * j < BP) {
+        sp_st(sc[w][0], cl[j], yk[j][0]);
+        sp_st(sc[w][1], cl[j], yk[j][1]);
+      }
+    wave_sync();
+    // M[r, :] = Y_a[r, :] U_a + Y_c[r, :] L_e
 #pragma unroll
-    for (int e = 0; e < NZ; ++e) {
-      cmac(mx, sc[w][0][ci[0][e][c]], cv[0][e][c]);
-      cmac(mx, sc[w][1][ci[1][e][c]], cv[1][e][c]);
+    for (int j = 0; j < NCL; ++j) {
+      const int c = cl[j] / sizeof(double2);
+      double2 mx = make_double2(0.0, 0.0);
+#pragma unroll
+      for (int e = 0; e < NZ; ++e) {
+        cmac(mx, sp_ld(sc[w][0], ci[0][e][c]), cv[0][e][c]);
+        cmac(mx, sp_ld(sc[w][1], ci[1][e][c]), cv[1][e][c]);
+      }
+      if (l + 64 * j < BP) sp_st(base, t.omx + cl[j], mx);
     }
-    if (l + 64 * j < BP) Omx[r * BP + c] = mx;
+    if (RPW > 1) wave_sync();   // the M gathers are done before the next row's G rows land
   }
 }
 
 }  // namespace
 
-void launch_cr_sp_fwd(const CrDims& c, double2* pool, const CrSpFwd* tasks, int n, const int* trow,
-                      const double2* tcv, const int* tcm, const double2* Delta, hipStream_t s) {
+void launch_cr_sp_fwd(const CrDims& c, double2* pool, const CrSpRowFwd* recs, int n, const double2* tcv,
+                      const int* tcm, const double2* Delta, hipStream_t s) {
   if (n <= 0) return;
-  const int nrb = c.BP / 2 / kSpRowsWG;
-  const dim3 g(n * nrb, c.nbatch), b(64 * kSpRowsWG);
+  const dim3 g(n * (c.BP / 2 / kSpRowsWG), c.nbatch), b(64 * kSpRowsWG);
   switch (c.BP) {
-    case 32: hipLaunchKernelGGL(k_cr_sp_fwd<32>, g, b, 0, s, pool, c.item, tasks, trow, tcv, tcm, Delta, 2 * c.N, c.P, nrb); break;
-    case 64: hipLaunchKernelGGL(k_cr_sp_fwd<64>, g, b, 0, s, pool, c.item, tasks, trow, tcv, tcm, Delta, 2 * c.N, c.P, nrb); break;
-    default: hipLaunchKernelGGL(k_cr_sp_fwd<96>, g, b, 0, s, pool, c.item, tasks, trow, tcv, tcm, Delta, 2 * c.N, c.P, nrb); break;
+    case 32: hipLaunchKernelGGL(k_cr_sp_fwd<32>, g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+    case 64: hipLaunchKernelGGL(k_cr_sp_fwd<64>, g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+    default: hipLaunchKernelGGL(k_cr_sp_fwd<96>, g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
   }
 }
 
-void launch_cr_sp_bwd(const CrDims& c, double2* pool, const CrSpBwd* tasks, int n, const int* trow,
-                      const double2* tcv, const int* tcm, const double2* Delta, hipStream_t s) {
+void launch_cr_sp_bwd(const CrDims& c, double2* pool, const CrSpRowBwd* recs, int n, const double2* tcv,
+                      const int* tcm, const double2* Delta, hipStream_t s) {
   if (n <= 0) return;
-  const int nrb = c.BP / 2 / kSpRowsWG;
-  const dim3 g(n * nrb, c.nbatch), b(64 * kSpRowsWG);
+  constexpr int RPW = SP_RPW_B;
+  const dim3 g(n * (c.BP / 2 / (kSpRowsWG * RPW)), c.nbatch), b(64 * kSpRowsWG);
   switch (c.BP) {
-    case 32: hipLaunchKernelGGL(k_cr_sp_bwd<32>, g, b, 0, s, pool, c.item, tasks, trow, tcv, tcm, Delta, 2 * c.N, c.P, nrb); break;
-    case 64: hipLaunchKernelGGL(k_cr_sp_bwd<64>, g, b, 0, s, pool, c.item, tasks, trow, tcv, tcm, Delta, 2 * c.N, c.P, nrb); break;
-    default: hipLaunchKernelGGL(k_cr_sp_bwd<96>, g, b, 0, s, pool, c.item, tasks, trow, tcv, tcm, Delta, 2 * c.N, c.P, nrb); break;
+    case 32: hipLaunchKernelGGL((k_cr_sp_bwd<32, RPW>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+    case 64: hipLaunchKernelGGL((k_cr_sp_bwd<64, RPW>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+    default: hipLaunchKernelGGL((k_cr_sp_bwd<96, RPW>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
   }
 }
 

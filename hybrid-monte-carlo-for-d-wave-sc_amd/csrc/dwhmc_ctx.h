@@ -100,10 +100,10 @@ struct dwh_ctx {
   double2* bpool = nullptr;   // CR block pool (nbatch x nblk blocks)
   dwh::CrTask* d_tasks = nullptr;
   dwh::CrSlot* d_slots = nullptr;
-  dwh::CrSpFwd* d_sp_fwd = nullptr;
-  dwh::CrSpBwd* d_sp_bwd = nullptr;
-  dwh::SpTaskArrays sp_arr;   // the sparse stages' per-task operand arrays
-  int *d_sp_row = nullptr, *d_sp_cm = nullptr;
+  dwh::SpTaskArrays sp_arr;   // the sparse stages' row records and per-task column arrays
+  dwh::CrSpRowFwd* d_sp_rf = nullptr;
+  dwh::CrSpRowBwd* d_sp_rb = nullptr;
+  int* d_sp_cm = nullptr;
   double2* d_sp_cv = nullptr;
   double* efpart = nullptr;     // per (chain, pole) E_f / Tr G22 partials
   unsigned* efdone = nullptr;   // per chain: pole blocks done (k_cr_fermion_energy)

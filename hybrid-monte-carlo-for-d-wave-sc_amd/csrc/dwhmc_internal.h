@@ -159,17 +159,48 @@ struct CrSpFwd {
 struct CrSpBwd {
   int gaa, gac, gca, gcc, ua, le, la, ue, oza, ozc, oya, oyc, omx, pad0, pad1, pad2;
 };
-// Per task (tasks[ti]), arrays of kCrSpNZ x BP entries for each of its sparse
-// operands, so a workgroup reads its patterns without first reading the
-// task: trow — the row-pattern words of the left sparse operands (forward:
-// U_k, L_er, L_el; backward: L_a, U_e); tcv / tcm — the column entries of the
-// right ones (forward: L_k, U_el, U_er; backward: U_a, L_e): static hopping
-// value with op applied, and meta = (Δ index + 1, 0 none) | op << 22 |
-// row << 24.  Delta: the chains' N x 2 Δ (batch item bi reads chain bi / P).
-void launch_cr_sp_fwd(const CrDims& c, double2* pool, const CrSpFwd* tasks, int n, const int* trow,
-                      const double2* tcv, const int* tcm, const double2* Delta, hipStream_t s);
-void launch_cr_sp_bwd(const CrDims& c, double2* pool, const CrSpBwd* tasks, int n, const int* trow,
-                      const double2* tcv, const int* tcm, const double2* Delta, hipStream_t s);
+// (CrSpFwd / CrSpBwd describe the tasks to the plan and its dataflow check;
+// the kernels read the records below instead.)
+//
+// Row records: what a wave needs for output row r of task ti, resolved on the
+// host (cr_sparse_task_arrays) into one 256-byte record at index ti * HP + r,
+// read with a few wide scalar loads.  Row r of every sparse left operand
+// (forward: U_k, L_er, L_el; backward: L_a, U_e) is kCrSpNZ slots in a fixed
+// order: kCrSpNZ - 1 hopping slots, then the pairing slot.
+//   hopping slot: hv — the static value (real; the forward stage's -U, -L sign
+//     applied; 0.0 in an empty slot), ho — the dense operand's stored row the
+//     entry multiplies, as a byte offset from the batch item's pool base
+//     ((block * HP * BP + row * BP) * sizeof(double2); an empty slot points
+//     at a valid row);
+//   pairing slot: the entry is ps * Δ[pd] (ps = ±1/2 with the stage's sign, 0
+//     when empty) and multiplies the synthesised bottom row HP + k of the
+//     dense operand, read from its stored row k at po (same offset form).
+// The other offsets are row r of the task's dense blocks in that form.
+struct alignas(256) CrSpRowFwd {
+  double hv[3][kCrSpNZ - 1];     // U_k, L_er, L_el
+  double ps[3];
+  uint32_t ho[3][kCrSpNZ - 1];   // rows of Dinv_er, Dinv_er, Dinv_el
+  uint32_t po[3], pd[3];
+  uint32_t dk, od, ou, ol;       // row r of D_k, D'_k, U'_k, L'_k
+};
+struct alignas(256) CrSpRowBwd {
+  double hv[2][kCrSpNZ - 1];        // L_a, U_e
+  double ps[2];
+  uint32_t ho[2][2][kCrSpNZ - 1];   // [operand][0 / 1]: rows of G_aa / G_ac (L_a), G_ca / G_cc (U_e)
+  uint32_t po[2][2], pd[2];
+  uint32_t g[4];                    // row r of G_aa, G_ca, G_ac, G_cc
+  uint32_t oza, ozc, oya, oyc, omx;
+};
+static_assert(sizeof(CrSpRowFwd) == 256 && sizeof(CrSpRowBwd) == 256, "one record: 256 bytes");
+// recs: the stage's first record (n tasks x HP rows).  tcv / tcm — per task,
+// [operand][entry][BP], the column entries of the sparse right operands
+// (forward: L_k, U_el, U_er; backward: U_a, L_e): static hopping value with op
+// applied, and meta = (Δ index + 1, 0 none) | op << 22 | row << 24.
+// Delta: the chains' N x 2 Δ (batch item bi reads chain bi / P).
+void launch_cr_sp_fwd(const CrDims& c, double2* pool, const CrSpRowFwd* recs, int n, const double2* tcv,
+                      const int* tcm, const double2* Delta, hipStream_t s);
+void launch_cr_sp_bwd(const CrDims& c, double2* pool, const CrSpRowBwd* recs, int n, const double2* tcv,
+                      const int* tcm, const double2* Delta, hipStream_t s);
 // block-product stage configuration: output tile TS x TS (16 or 32) and the
 // number of waves splitting each tile's K range (1, 2, 4)
 struct CrGemmCfg {

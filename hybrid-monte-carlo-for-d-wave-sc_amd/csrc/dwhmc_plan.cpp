@@ -22,15 +22,64 @@
 
 namespace dwh {
 
-SpTaskArrays cr_sparse_task_arrays(const CrPlan& pl, int BP, const std::vector<double2>& colval,
-                                   const std::vector<int>& colsrc) {
+namespace {
+// Top-half row r of level-0 block b (U[y]: Ly + y, L[y]: 2 Ly + y) in the
+// records' canonical slot order (cr_sparse_patterns guarantees it fits):
+// hopping entries (particle columns k < HP) with their static values, exactly
+// as k_cr_fill resolves them (the last matching table slot), then the one
+// pairing entry (hole column HP + k): the Δ index whose Δ/2 the pool holds.
+struct SpRow {
+  double hv[dwh::kCrSpNZ - 1] = {};
+  int hk[dwh::kCrSpNZ - 1] = {};   // dense operand row of each hopping slot (0: empty)
+  double ps = 0.0;                 // 1/2, or 0: no pairing entry
+  int pk = 0, pd = 0;              // pairing: dense operand row HP + pk, Δ index
+};
+SpRow sp_row(const std::vector<int>& rowpat, int b, int r, int Lx, int Ly, int BP, const std::vector<int>& hcol,
+             const std::vector<double>& hval, const std::vector<int>& Dcol, const std::vector<int>& Dsrc) {
+  const int NZ = dwh::kCrSpNZ, HP = BP / 2, t = b / Ly, y = b % Ly;
+  const int yr = (t == 2) ? (y + 1) % Ly : y, yc = (t == 1) ? (y + 1) % Ly : y;
+  SpRow s;
+  int nh = 0;
+  for (int e = 0; e < NZ; ++e) {
+    const int w = rowpat[((size_t)b * NZ + e) * BP + r];
+    if (((w >> 22) & 3) == 3) continue;
+    const int k = (w >> 14) & 0xff, i = yr * Lx + r;   // top rows: op 0, the stored element (r, k)
+    if (k < HP) {
+      if (nh >= NZ - 1) continue;
+      const int j = yc * Lx + k;
+      double h = 0.0;
+      for (int sl = 0; sl < kHSlots; ++sl)
+        if (hcol[(size_t)i * kHSlots + sl] == j) h = hval[(size_t)i * kHSlots + sl];
+      s.hv[nh] = h;
+      s.hk[nh++] = k;
+    } else {
+      const int j = yc * Lx + (k - HP);
+      int src = -1;
+      for (int sl = 0; sl < kSlots; ++sl)
+        if (Dcol[(size_t)i * kSlots + sl] == j) src = Dsrc[(size_t)i * kSlots + sl];
+      s.pk = k - HP;
+      if (src >= 0) {
+        s.ps = 0.5;
+        s.pd = src;
+      }
+    }
+  }
+  return s;
+}
+}  // namespace
+
+SpTaskArrays cr_sparse_task_arrays(const CrPlan& pl, int Lx, int Ly, int BP, const std::vector<int>& hcol,
+                                   const std::vector<double>& hval, const std::vector<int>& Dcol,
+                                   const std::vector<int>& Dsrc) {
   const int NZ = dwh::kCrSpNZ, E = NZ * BP, HP = BP / 2;
   SpTaskArrays a;
-  auto rows = [&](std::initializer_list<int> rbs) {   // [r][operand][entry]
-    for (int r = 0; r < HP; ++r)
-      for (int rb : rbs)
-        for (int e = 0; e < NZ; ++e) a.row.push_back(pl.rowpat[(size_t)rb * E + (size_t)e * BP + r]);
-  };
+  if (pl.colpat.empty()) return a;
+  std::vector<double2> colval;
+  std::vector<int> colsrc;
+  cr_sparse_colvals(pl.colpat, Lx, Ly, BP, hcol, hval, Dcol, Dsrc, colval, colsrc);
+  auto row = [&](int b, int r) { return sp_row(pl.rowpat, b, r, Lx, Ly, BP, hcol, hval, Dcol, Dsrc); };
+  // byte offset of row k of pool block b from the batch item's base
+  auto at = [&](int b, int k) { return (uint32_t)(((int64_t)b * HP + k) * BP * (int64_t)sizeof(double2)); };
   auto cols = [&](int cb) {
     for (int k = cb * E; k < (cb + 1) * E; ++k) {
       const int w = pl.colpat[k], op = (w >> 22) & 3, idx = (w >> 14) & 0xff, src = colsrc[k];
@@ -39,15 +88,55 @@ SpTaskArrays cr_sparse_task_arrays(const CrPlan& pl, int BP, const std::vector<d
     }
   };
   for (const dwh::CrSpFwd& t : pl.sp_fwd) {
-    rows({t.uk, t.ler, t.lel});
+    const int sparse[3] = {t.uk, t.ler, t.lel}, dense[3] = {t.dir, t.dir, t.dil};
+    for (int r = 0; r < HP; ++r) {
+      dwh::CrSpRowFwd q{};
+      for (int o = 0; o < 3; ++o) {
+        const SpRow s = row(sparse[o], r);
+        for (int e = 0; e < NZ - 1; ++e) {
+          q.hv[o][e] = -s.hv[e];   // V = -U Dinv, -L Dinv
+          q.ho[o][e] = at(dense[o], s.hk[e]);
+        }
+        q.ps[o] = -s.ps;
+        q.po[o] = at(dense[o], s.pk);
+        q.pd[o] = (uint32_t)s.pd;
+      }
+      q.dk = at(t.dk, r);
+      q.od = at(t.od, r);
+      q.ou = at(t.ou, r);
+      q.ol = at(t.ol, r);
+      a.rf.push_back(q);
+    }
     cols(t.lk);
     cols(t.uel);
     cols(t.uer);
   }
-  a.row_bwd0 = a.row.size();
   a.col_bwd0 = a.cv.size();
   for (const dwh::CrSpBwd& t : pl.sp_bwd) {
-    rows({t.la, t.ue});
+    const int sparse[2] = {t.la, t.ue}, dense[2][2] = {{t.gaa, t.gac}, {t.gca, t.gcc}};
+    for (int r = 0; r < HP; ++r) {
+      dwh::CrSpRowBwd q{};
+      for (int o = 0; o < 2; ++o) {
+        const SpRow s = row(sparse[o], r);
+        for (int g = 0; g < 2; ++g) {
+          for (int e = 0; e < NZ - 1; ++e) q.ho[o][g][e] = at(dense[o][g], s.hk[e]);
+          q.po[o][g] = at(dense[o][g], s.pk);
+        }
+        for (int e = 0; e < NZ - 1; ++e) q.hv[o][e] = s.hv[e];
+        q.ps[o] = s.ps;
+        q.pd[o] = (uint32_t)s.pd;
+      }
+      q.g[0] = at(t.gaa, r);
+      q.g[1] = at(t.gca, r);
+      q.g[2] = at(t.gac, r);
+      q.g[3] = at(t.gcc, r);
+      q.oza = at(t.oza, r);
+      q.ozc = at(t.ozc, r);
+      q.oya = at(t.oya, r);
+      q.oyc = at(t.oyc, r);
+      q.omx = at(t.omx, r);
+      a.rb.push_back(q);
+    }
     cols(t.ua);
     cols(t.le);
   }
@@ -62,7 +151,9 @@ namespace {
 // block: row x of the top half, and row HP + x synthesised from it (M-form:
 // [conj B | -conj A]).  Entry = top-half offset | (column for rowpat, row for
 // colpat) << 14 | op << 22 (op 0 as stored, 1 conj, 2 -conj, 3 empty).  False when a
-// row or column holds more than kCrSpNZ entries (the dense level 0 then runs).
+// row or column holds more than kCrSpNZ entries, or a top-half row more than
+// kCrSpNZ - 1 hopping entries or more than one pairing entry (the dense level
+// 0 then runs).
 bool cr_sparse_patterns(int Lx, int Ly, int BP, const std::vector<int>& hcol, const std::vector<int>& Dcol,
                         std::vector<int>& rowpat, std::vector<int>& colpat) {
   const int HP = BP / 2, NZ = dwh::kCrSpNZ;
@@ -86,6 +177,11 @@ bool cr_sparse_patterns(int Lx, int Ly, int BP, const std::vector<int>& hcol, co
           if (j >= 0 && j / Lx == yc) top.insert({x, HP + j % Lx});
         }
       }
+      // canonical form of the row records (dwh::CrSpRowFwd / Bwd): a top-half
+      // row holds at most NZ - 1 hopping entries and one pairing entry
+      std::vector<int> nhop(HP, 0), npair(HP, 0);
+      for (const auto& xc : top)
+        if (++(xc.second < HP ? nhop : npair)[xc.first] > (xc.second < HP ? NZ - 1 : 1)) return false;
       std::vector<int> rn(BP, 0), cn(BP, 0);
       auto put = [&](int r, int c, int off, int op) {
         if (rn[r] >= NZ || cn[c] >= NZ) return false;
@@ -993,6 +1089,8 @@ int plan_cr(int64_t Lx, int64_t Ly, int P, int nbatch, const std::vector<int>& D
   c.item = (int64_t)c.nblk * (c.BP / 2) * c.BP;
   if ((uint64_t)c.item >= (uint64_t)dwh::kCrNone)
     return fail(nullptr, DWH_ERR_ARG, "CR pool: a batch item exceeds 2^32 elements (32-bit block-product offsets)");
+  if (!pl.sp_fwd.empty() && (uint64_t)c.item * sizeof(double2) >= (uint64_t)dwh::kCrNone)
+    return fail(nullptr, DWH_ERR_ARG, "CR pool: a batch item exceeds 2^32 bytes (32-bit sparse row offsets)");
   pl.slots.clear();
   for (CrStage& st : pl.stages) {
     if (st.kind != 1) continue;

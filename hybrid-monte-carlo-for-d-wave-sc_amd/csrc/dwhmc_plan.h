@@ -52,20 +52,24 @@ struct CrPlan {
 };
 
 // The sparse stages' per-task operand arrays (launch_cr_sp_fwd / _bwd,
-// dwhmc_internal.h).  Per task: the row-pattern words of its left sparse
-// operands, laid out [row r < HP][operand][entry] so a wave reads its row's
-// words (and then their values) with scalar loads (row); and the column
-// entries of its right operands, [operand][entry][column], value (cv) and
-// meta word (cm: Δ index + 1 | op << 22 | row << 24), read coalesced.
-// Forward tasks first; the backward ones from row_bwd0 / col_bwd0.
+// dwhmc_internal.h).  Per task: one host-resolved record per output row
+// (rf / rb: [task][row r < HP], dwh::CrSpRowFwd / CrSpRowBwd) holding the row
+// of each left sparse operand and the task's dense row offsets; and the
+// column entries of its right operands, [operand][entry][column], value (cv)
+// and meta word (cm: Δ index + 1 | op << 22 | row << 24), read coalesced
+// (forward tasks first; the backward ones from col_bwd0).
 struct SpTaskArrays {
-  std::vector<int> row, cm;
+  std::vector<dwh::CrSpRowFwd> rf;
+  std::vector<dwh::CrSpRowBwd> rb;
+  std::vector<int> cm;
   std::vector<double2> cv;
-  size_t row_bwd0 = 0, col_bwd0 = 0;
+  size_t col_bwd0 = 0;
 };
 
-SpTaskArrays cr_sparse_task_arrays(const CrPlan& pl, int BP, const std::vector<double2>& colval,
-                                   const std::vector<int>& colsrc);
+// Lx, Ly: the CR lattice (CrDims); the tables are the host model's
+SpTaskArrays cr_sparse_task_arrays(const CrPlan& pl, int Lx, int Ly, int BP, const std::vector<int>& hcol,
+                                   const std::vector<double>& hval, const std::vector<int>& Dcol,
+                                   const std::vector<int>& Dsrc);
 // column-pattern values of the level-0 U / L blocks (static hopping value, or
 // the Δ index of a pairing entry) in the kernels' [block][entry][BP] order
 void cr_sparse_colvals(const std::vector<int>& colpat, int Lx, int Ly, int BP, const std::vector<int>& hcol,

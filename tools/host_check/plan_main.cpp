@@ -16,7 +16,9 @@
 // (a) build_host_model's tables on small and degenerate lattices against a
 // dense restatement of the reference, (b) its refusals with their texts,
 // (c) the dispatch-ordered slots plan_cr builds for the hottest kernel, over
-// the same configurations.  Exit status 0: every check passed (and no
+// the same configurations, (d) the sparse level-0 stages' row records against
+// a dense restatement of the level-0 U / L blocks, and the canonical-form
+// rejection.  Exit status 0: every check passed (and no
 // sanitizer report).
 #include <cmath>
 #include <cstdint>
@@ -69,8 +71,8 @@ struct Tables {
       }
     for (int i = 0; i < 2 * N; ++i) dis[i] = 0.8 * std::sin(1.0 + 0.37 * i);
   }
-  int build(dwh::HostModel* m, bool lanczos = true) const {
-    return dwh::build_host_model(Lx, Ly, 1.0, -0.35, -1.08, nn.data(), nnn.data(), 2, dis.data(), m, lanczos);
+  int build(dwh::HostModel* m, bool lanczos = true, double tp = -0.35) const {
+    return dwh::build_host_model(Lx, Ly, 1.0, tp, -1.08, nn.data(), nnn.data(), 2, dis.data(), m, lanczos);
   }
 };
 
@@ -245,6 +247,151 @@ void check_slots(const dwh::CrDims& c, const dwh::CrPlan& pl, int Lx, int Ly, in
   if (covered != pl.slots.size()) flunk("slots: array size", Lx, Ly, (long)covered, (long)pl.slots.size());
 }
 
+// (d) the row records of the sparse level-0 stages (cr_sparse_task_arrays):
+// every top-half row of every level-0 U[y] = A[y, y+1] / L[y] = A[y+1, y]
+// rebuilt from the records' slots equals the dense restatement (h in the
+// reference's loop order, later writes winning; the pairing source index),
+// with the forward stage's sign; every offset is a row start inside the block
+// it is meant for.  Blocks are rows of the CR lattice (rows lattice rows each).
+int sparse_stages(const dwh::CrPlan& pl) {
+  int n = 0;
+  for (const dwh::CrStage& st : pl.stages) n += st.kind == 2;
+  return n;
+}
+void check_records(int Lx, int Ly, double tp) {
+  using namespace dwh;
+  const Tables T(Lx, Ly);
+  const int N = T.N;
+  HostModel m;
+  if (T.build(&m, false, tp) != DWH_OK) return flunk("records: build_host_model", Lx, Ly);
+  CrDims c;
+  CrPlan pl;
+  if (plan_cr(Lx, Ly, 7, 14, m.Dcol, m.hcol, 1, 1, 256, &c, &pl) != DWH_OK) return flunk("records: plan_cr", Lx, Ly);
+  if (sparse_stages(pl) != 2) return flunk("records: not a sparse level 0", Lx, Ly, sparse_stages(pl));
+  const SpTaskArrays a = cr_sparse_task_arrays(pl, c.Lx, c.Ly, c.BP, m.hcol, m.hval, m.Dcol, m.Dsrc);
+  const int HP = c.BP / 2, Lc = c.Lx, Lyc = c.Ly;
+  if (a.rf.size() != pl.sp_fwd.size() * HP || a.rb.size() != pl.sp_bwd.size() * HP)
+    return flunk("records: count", Lx, Ly, (long)a.rf.size(), (long)a.rb.size());
+  auto NN = [&](int i, int dir) { return (int)T.nn[(size_t)dir * N + i] - 1; };
+  auto NNN = [&](int i, int dir) { return (int)T.nnn[(size_t)dir * N + i] - 1; };
+  std::vector<double> h((size_t)N * N, 0.0);
+  std::vector<int> src((size_t)N * N, -1);
+  for (int i = 0; i < N; ++i) {
+    for (int dir = 0; dir < 4; ++dir)
+      if (NN(i, dir) > i) h[(size_t)i * N + NN(i, dir)] = -1.0;
+    for (int dir = 0; dir < 4; ++dir)
+      if (NNN(i, dir) > i) h[(size_t)i * N + NNN(i, dir)] = -tp;
+  }
+  for (int i = 0; i < N; ++i)
+    for (int j = i + 1; j < N; ++j) h[(size_t)j * N + i] = h[(size_t)i * N + j];
+  for (int i = 0; i < N; ++i)
+    for (int dir = 0; dir < 2; ++dir) {
+      const int j = NN(i, dir);
+      src[(size_t)i * N + j] = i + N * dir;
+      src[(size_t)j * N + i] = i + N * dir;
+    }
+  const uint64_t rowb = (uint64_t)c.BP * sizeof(double2), blkb = rowb * HP;
+  std::vector<char> covered(3 * Lyc, 0);
+  // row r of sparse level-0 block sb (record slots hv / ho / ps / po / pd,
+  // values times sg) against the dense rows; the slots address rows of block db
+  auto row = [&](int sb, int r, const double* hv, const uint32_t* const* ho, int nho, double ps,
+                 const uint32_t* const* po, uint32_t pd, double sg, const int* db) {
+    const int t = sb / Lyc, y = sb % Lyc;
+    if (t < 1 || t > 2) return flunk("records: sparse operand is not a level-0 U / L", Lx, Ly, sb);
+    covered[sb] = 1;
+    const int yr = (t == 2) ? (y + 1) % Lyc : y, yc = (t == 1) ? (y + 1) % Lyc : y;
+    std::vector<double> got(HP, 0.0), want(HP, 0.0);
+    int wk = -1, wsrc = -1;
+    if (r < Lc)
+      for (int k = 0; k < Lc; ++k) {
+        const int i = yr * Lc + r, j = yc * Lc + k;
+        want[k] = h[(size_t)i * N + j];
+        if (src[(size_t)i * N + j] >= 0) {
+          if (wk >= 0) flunk("records: two pairing partners in one row", Lx, Ly, sb, r);
+          wk = k;
+          wsrc = src[(size_t)i * N + j];
+        }
+      }
+    for (int e = 0; e < kCrSpNZ - 1; ++e) {
+      int k = -1;
+      for (int g = 0; g < nho; ++g) {
+        const uint64_t o = ho[g][e], b0 = (uint64_t)db[g] * blkb;
+        if (o < b0 || o >= b0 + blkb || (o - b0) % rowb) return flunk("records: hopping offset outside its block", Lx, Ly, sb, r);
+        if (g && (int)((o - b0) / rowb) != k) flunk("records: the two dense rows of a slot differ", Lx, Ly, sb, r);
+        k = (int)((o - b0) / rowb);
+      }
+      got[k] += sg * hv[e];
+    }
+    for (int k = 0; k < HP; ++k)
+      if (got[k] != want[k]) flunk("records: hopping row", Lx, Ly, sb, r);
+    int pk = -1;
+    for (int g = 0; g < nho; ++g) {
+      const uint64_t o = po[g][0], b0 = (uint64_t)db[g] * blkb;
+      if (o < b0 || o >= b0 + blkb || (o - b0) % rowb) return flunk("records: pairing offset outside its block", Lx, Ly, sb, r);
+      if (g && (int)((o - b0) / rowb) != pk) flunk("records: the two dense rows of the pairing slot differ", Lx, Ly, sb, r);
+      pk = (int)((o - b0) / rowb);
+    }
+    if (pd >= (uint32_t)(2 * N)) return flunk("records: pairing index outside Delta", Lx, Ly, sb, r);
+    if (wk < 0 ? ps != 0.0 : (sg * ps != 0.5 || pk != wk || (int)pd != wsrc)) flunk("records: pairing slot", Lx, Ly, sb, r);
+  };
+  auto in_row = [&](uint32_t o, int b, int r) { return (uint64_t)o == (uint64_t)b * blkb + (uint64_t)r * rowb; };
+  for (size_t ti = 0; ti < pl.sp_fwd.size(); ++ti) {
+    const CrSpFwd& t = pl.sp_fwd[ti];
+    const int sparse[3] = {t.uk, t.ler, t.lel}, dense[3] = {t.dir, t.dir, t.dil};
+    for (int r = 0; r < HP; ++r) {
+      const CrSpRowFwd& q = a.rf[ti * HP + r];
+      for (int o = 0; o < 3; ++o) {
+        const uint32_t *ho = q.ho[o], *po = &q.po[o];
+        row(sparse[o], r, q.hv[o], &ho, 1, q.ps[o], &po, q.pd[o], -1.0, &dense[o]);
+      }
+      if (!in_row(q.dk, t.dk, r) || !in_row(q.od, t.od, r) || !in_row(q.ou, t.ou, r) || !in_row(q.ol, t.ol, r))
+        flunk("records: forward dense rows", Lx, Ly, (long)ti, r);
+    }
+  }
+  for (size_t ti = 0; ti < pl.sp_bwd.size(); ++ti) {
+    const CrSpBwd& t = pl.sp_bwd[ti];
+    const int sparse[2] = {t.la, t.ue}, dense[2][2] = {{t.gaa, t.gac}, {t.gca, t.gcc}};
+    for (int r = 0; r < HP; ++r) {
+      const CrSpRowBwd& q = a.rb[ti * HP + r];
+      for (int o = 0; o < 2; ++o) {
+        const uint32_t *ho[2] = {q.ho[o][0], q.ho[o][1]}, *po[2] = {&q.po[o][0], &q.po[o][1]};
+        row(sparse[o], r, q.hv[o], ho, 2, q.ps[o], po, q.pd[o], 1.0, dense[o]);
+      }
+      if (!in_row(q.g[0], t.gaa, r) || !in_row(q.g[1], t.gca, r) || !in_row(q.g[2], t.gac, r) ||
+          !in_row(q.g[3], t.gcc, r) || !in_row(q.oza, t.oza, r) || !in_row(q.ozc, t.ozc, r) ||
+          !in_row(q.oya, t.oya, r) || !in_row(q.oyc, t.oyc, r) || !in_row(q.omx, t.omx, r))
+        flunk("records: backward dense rows", Lx, Ly, (long)ti, r);
+    }
+  }
+  for (int b = Lyc; b < 3 * Lyc; ++b)
+    if (!covered[b]) flunk("records: a level-0 U / L block no record reads", Lx, Ly, b);
+}
+
+// a top-half row the records cannot hold — a second pairing partner, or a
+// fourth hopping partner, in the neighbouring row — makes the plan run the
+// dense level 0, exactly as an over-full row does
+void check_canonical_rejection() {
+  const int Lx = 20, Ly = 4;
+  dwh::HostModel m;
+  if (Tables(Lx, Ly).build(&m, false) != DWH_OK) return flunk("rejection: build_host_model", Lx, Ly);
+  dwh::CrDims c;
+  dwh::CrPlan pl;
+  auto stages = [&](const std::vector<int>& Dcol, const std::vector<int>& hcol) {
+    return dwh::plan_cr(Lx, Ly, 7, 14, Dcol, hcol, 1, 1, 256, &c, &pl) == DWH_OK ? sparse_stages(pl) : -1;
+  };
+  if (stages(m.Dcol, m.hcol) != 2) flunk("rejection: the plain lattice is sparse-capable", Lx, Ly);
+  // site 0: its same-row partner (site 1) replaced by a site of the next row
+  std::vector<int> Dcol = m.Dcol, hcol = m.hcol;
+  bool did = false;
+  for (int s = 0; s < dwh::kSlots; ++s)
+    if (Dcol[s] == 1) Dcol[s] = Lx + 5, did = true;
+  if (!did || stages(Dcol, m.hcol) != 0) flunk("rejection: two pairing entries in a top-half row", Lx, Ly);
+  did = false;
+  for (int s = 1; s < dwh::kHSlots; ++s)
+    if (hcol[s] == 1) hcol[s] = Lx + 5, did = true;
+  if (!did || stages(m.Dcol, hcol) != 0) flunk("rejection: four hopping entries in a top-half row", Lx, Ly);
+}
+
 }  // namespace
 
 int main() {
@@ -337,6 +484,16 @@ int main() {
       }
     }
   if (nslotconf != nconf) flunk("slot configurations", nslotconf, nconf);
+
+  // (d) row records: t' = 0 (empty hopping slots), Lx = 3 (x - 1 = x + 1 + wrap,
+  // grouped rows), 8 x 8 (two-row blocks), Ly = 4 with a padded (Lx = 20) and an
+  // exactly filled (Lx = 32) BP = 64, BP = 96 (Lx = 40), and a longer chain
+  setenv("DWHMC_CR_SPARSE0", "1", 1);
+  setenv("DWHMC_CR_MERGE", "8", 1);
+  const int reclat[][2] = {{20, 4}, {3, 16}, {3, 20}, {8, 8}, {32, 4}, {40, 4}, {16, 4}, {20, 6}, {32, 32}};
+  for (const auto& l : reclat)
+    for (double tp : {-0.35, 0.0}) check_records(l[0], l[1], tp);
+  check_canonical_rejection();
   std::printf("plan_main: %d plan configurations, %d failure(s)\n", nconf, failures);
   return failures ? 1 : 0;
 }
