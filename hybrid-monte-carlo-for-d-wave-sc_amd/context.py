@@ -264,6 +264,39 @@ class FermionContext:
                      dos_AN=dos_an[k].copy(), A_k_omega0=ak[k].reshape(Ly, Lx).T.copy())
                 for k in range(ns)]
 
+    def measure_spectral_maps(self, eta: float, domega: float, omega_max: float, first: int = 0,
+                              count: int | None = None, stride: int = 1, chain: int = 0, deltas=None,
+                              ldos: bool = True, akw: bool = True) -> dict:
+        """LDOS(i, ω) and A(k, ω) (dwh_measure_spectral_maps) on the window
+        first + q·stride, q < count, of the DOS grid -ω_max:Δω:ω_max
+        (count=None: up to the end of the grid), at the device Δ of `chain`
+        or at the pairing fields `deltas` ((nstates, N, 2)) on its lattice
+        and disorder.  Returns omega (count,) and, unless switched off, ldos
+        and akw of shape (nstates, count, Ly, Lx): ldos[s, q, y, x] at site
+        i = x + Lx·y, akw[s, q, ky, kx]."""
+        first, stride = int(first), int(stride)
+        omega = spectral_window(eta, domega, omega_max, first, count, stride, self._lib)
+        count = len(omega)
+        d, ns = None, 1
+        if deltas is not None:
+            D = np.asarray(deltas, dtype=np.complex128)
+            if D.ndim != 3 or D.shape[1:] != (self.N, 2) or D.shape[0] < 1:
+                raise ValueError(f"expected (nstates, {self.N}, 2) pairing fields")
+            ns = D.shape[0]
+            d = np.ascontiguousarray(np.transpose(D, (0, 2, 1)))
+        Lx, Ly = self.info_lattice
+        out_l = np.empty((ns, count, Ly, Lx)) if ldos else None
+        out_a = np.empty((ns, count, Ly, Lx)) if akw else None
+        self._c(self._lib.dwh_measure_spectral_maps(self._h, int(chain), ns, ptr(d), float(eta), float(domega),
+                                                    float(omega_max), first, count, stride, ptr(out_l),
+                                                    ptr(out_a)))
+        res = dict(omega=omega)
+        if ldos:
+            res["ldos"] = out_l
+        if akw:
+            res["akw"] = out_a
+        return res
+
     # -- assembly read-back (parity tests) --------------------------------
     def debug_dense_H(self, chain: int = 0) -> np.ndarray:
         """H_BdG(Δ) (2N, 2N) as the eigen/transport path assembles it (dwh_debug_dense_H)."""
@@ -283,7 +316,7 @@ class FermionContext:
 
     # -- timing ----------------------------------------------------------
     TIMERS = ("gj_update", "gj_pivot", "assemble", "contract", "step", "gj_edge", "cr_gemm", "cr_inv",
-              "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse")
+              "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral")
 
     def timing_enable(self, on=True):
         """on: True (all timers), False, or an iterable of timer names."""
@@ -317,6 +350,23 @@ def transport_grid(eta: float, domega: float, omega_max: float, lib=None):
     nw, nd = C.c_int64(), C.c_int64()
     check(lib.dwh_transport_grid(float(eta), float(domega), float(omega_max), C.byref(nw), C.byref(nd)))
     return nw.value, nd.value
+
+
+def spectral_window(eta: float, domega: float, omega_max: float, first: int = 0, count: int | None = None,
+                    stride: int = 1, lib=None) -> np.ndarray:
+    """Frequencies of the window first + q·stride, q < count, of the DOS grid
+    -ω_max:Δω:ω_max (dwh_spectral_window; host arithmetic, no device);
+    count=None: up to the end of the grid.  ValueError if the window leaves
+    the grid."""
+    lib = _lib.load() if lib is None else lib
+    first, stride = int(first), int(stride)
+    if count is None:
+        _, nd = transport_grid(eta, domega, omega_max, lib)
+        count = (nd - 1 - first) // stride + 1 if 0 <= first < nd and stride >= 1 else 0
+    count = int(count)
+    omega = np.empty(max(count, 0))
+    check(lib.dwh_spectral_window(float(eta), float(domega), float(omega_max), first, count, stride, ptr(omega)))
+    return omega
 
 
 def selftest_mfma(device: int = 0) -> int:

@@ -22,13 +22,14 @@ namespace dwh {
 
 enum TimerName {
   T_GJ_UPDATE = 0, T_GJ_PIVOT, T_ASSEMBLE, T_CONTRACT, T_STEP, T_GJ_EDGE, T_CR_GEMM, T_CR_INV, T_CR_INVSIDE,
-  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_COUNT
+  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_COUNT
 };
 inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assemble", "contract",
                                                  "step",      "gj_edge",  "cr_gemm",  "cr_inv",
                                                  "cr_inv_side",
                                                  "eig_own",   "eig_vendor",   // eigensolves (work: matrices)
-                                                 "cr_sparse"};
+                                                 "cr_sparse",
+                                                 "spectral"};   // LDOS / A(k, ω) map stage (work: flops)
 
 enum Algo { ALGO_DENSE = 0, ALGO_CR = 1, ALGO_EIG = 2 };
 
@@ -133,6 +134,11 @@ struct dwh_ctx {
   int64_t tr_nw = -1, tr_nd = -1;   // ω / DOS grid lengths the output buffers hold
   double2* d_tr_stage = nullptr;     // Δ snapshots of dwh_measure_transport_deltas
   int64_t tr_nstage = 0;
+  // spectral maps (dwh_measure_spectral_maps) workspace for sp_slots states:
+  // the Lorentzian table of one frequency chunk (2N x kSpChunk per state)
+  // and the two maps' output tiles (N x kSpChunk each per state)
+  int sp_slots = 0;
+  double *d_sp_lam = nullptr, *d_sp_out = nullptr;
   // own eigensolver (dwhmc_eig.hip) workspace for eig_slots matrices: hemv
   // partials, v ping-pong, w, tridiagonal (d, e), tau, compact-WY T blocks and
   // the back-transform's two nb x n products; the n x n work lives in the

@@ -328,6 +328,27 @@ void launch_tr_current(const double2* U, double2* JU, int N, const int* rowptr, 
 void launch_tr_reduce(const TrBufs& b, int N, int Lx, int Ly, double beta, double eta,
                       const TrGrid& g, bool ph, hipStream_t s);
 
+// Spectral maps LDOS(i, ω) / A(k, ω) (dwhmc_spectral.hip), every launch
+// batched over m states at the given per-state strides (elements).
+// Frequencies per chunk of the window: bounds the Lorentzian table (2N x
+// kSpChunk doubles per state) and the two output tiles (N x kSpChunk each)
+constexpr int kSpChunk = 1024;
+// Λ[n, q] = L(ω_q - E_n) at Lam[q + ldq n], q < cnt, n < n2; ω_q = point
+// first + q stride of the grid d0 + k dw (E: n2 per state)
+void launch_sp_lorentz(const double* E, int n2, double eta, double d0, double dw, int64_t first, int64_t stride,
+                       int cnt, double* Lam, int ldq, int64_t sLam, int m, hipStream_t s);
+// X[:, n] = unnormalised forward 2-D DFT of the particle rows of column n of U
+// (n2 x n2, ld n2) as an Lx x Ly image, for all 2N columns; T: scratch, X: N x
+// n2 (ld N) each
+void launch_sp_dft(const double2* U, int64_t sU, int Lx, int Ly, double2* T, int64_t sT, double2* X, int64_t sX,
+                   int m, hipStream_t s);
+// W[r + M n] = |X[r + ldx n]|², r < M, n < K
+void launch_sp_sqmod(const double2* X, int ldx, int64_t sX, int M, int K, double* W, int64_t sW, int m,
+                     hipStream_t s);
+// out[r + ldo q] = scale Σ_{n<K} |X[r + ldx n]|² Lam[q + ldq n], r < M, q < Q (fp64 MFMA)
+void launch_sp_maps(const double2* X, int ldx, int64_t sX, const double* Lam, int ldq, int64_t sLam, int M, int Q,
+                    int K, double scale, double* out, int ldo, int64_t sOut, int m, hipStream_t s);
+
 // Eigendecomposition leapfrog step (algo eig; U, JU, rho: nc chains of n2 x n2
 // column-major, E: nc x n2): JU = U diag(logistic(-β E)); after rho = JU U^H,
 // P at the bonds, Tr ρ_hh and E_f per chain

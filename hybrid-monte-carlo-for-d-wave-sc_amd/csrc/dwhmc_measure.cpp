@@ -798,6 +798,112 @@ int q_heev_enqueue(dwh_ctx* ctx, const TrSrc& src, int m, bool* done) {
   return DWH_OK;
 }
 
+// the nstates Δ snapshots of a _deltas call (finite, else DWH_ERR_ARG) into
+// the staging buffer (grown on demand)
+int stage_deltas(dwh_ctx* ctx, int64_t nstates, const dwh_c128* Delta) {
+  const int64_t n2 = 2 * (int64_t)ctx->d.N;
+  for (int64_t e = 0; e < nstates * n2; ++e)
+    if (!std::isfinite(Delta[e].re) || !std::isfinite(Delta[e].im)) return fail(ctx, DWH_ERR_ARG, "non-finite Delta");
+  if (nstates > ctx->tr_nstage) {
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    drop_alloc(ctx, ctx->d_tr_stage);
+    ctx->d_tr_stage = nullptr;
+    ctx->tr_nstage = 0;
+    if (int rc = dalloc(ctx, &ctx->d_tr_stage, (size_t)nstates * n2)) return rc;
+    ctx->tr_nstage = nstates;
+  }
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_tr_stage, Delta, (size_t)nstates * n2 * sizeof(double2),
+                               hipMemcpyHostToDevice, ctx->stream));
+  return DWH_OK;
+}
+
+// states per batched eigensolve of a _deltas / batched call: groups whose
+// three n2 x n2 work matrices fit in 16 GiB
+int tr_group(const dwh_ctx* ctx, int64_t n) {
+  const int N = ctx->d.N;
+  const double per = 3.0 * 16.0 * 4.0 * N * (double)N;
+  return std::max(1, (int)std::min<int64_t>(n, (int64_t)(16.0 * (1 << 30) / per)));
+}
+
+// LDOS(i, ω) and A(k, ω) (dwhmc_spectral.hip) of the m states of src on the
+// window first + q stride, q < count, of the DOS grid: one eigensolve, the
+// DFT of every column (akw), then per chunk of kSpChunk frequencies one
+// Lorentzian table shared by both maps and one product per map, copied out
+// chunk by chunk.  ldos / akw: host, N x count per state (either nullable).
+// The product: |X|² written out (k_sp_sqmod) and gemm_d (unset or
+// DWHMC_SPECTRAL_FUSED=0), or the fused k_sp_maps (=1), which the in-process
+// A/B at L = 32 found slower (profiles/spectral_maps_L32.txt).
+int spectral_run(dwh_ctx* ctx, const TrSrc& src, int m, double eta, double domega, double omega_max, int64_t first,
+                 int64_t count, int64_t stride, double* ldos, double* akw) {
+  int rc;
+  if ((rc = transport_prepare(ctx, std::max<int64_t>(ctx->tr_nw, 0), std::max<int64_t>(ctx->tr_nd, 0), m)))
+    return rc;
+  const int N = ctx->d.N, n2 = 2 * N;
+  const int64_t sA = (int64_t)n2 * n2, sLam = (int64_t)n2 * kSpChunk, sTile = (int64_t)N * kSpChunk, sOut = 2 * sTile;
+  if (m > ctx->sp_slots) {
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    drop_alloc(ctx, ctx->d_sp_lam);
+    drop_alloc(ctx, ctx->d_sp_out);
+    ctx->d_sp_lam = ctx->d_sp_out = nullptr;
+    ctx->sp_slots = 0;
+    if ((rc = dalloc(ctx, &ctx->d_sp_lam, (size_t)m * sLam)) || (rc = dalloc(ctx, &ctx->d_sp_out, (size_t)m * sOut)))
+      return rc;
+    ctx->sp_slots = m;
+  }
+  if ((rc = eigen_solve(ctx, src, m))) return rc;
+  const char* fe = std::getenv("DWHMC_SPECTRAL_FUSED");
+  const bool fused = fe && *fe == '1';
+  const dwh::TrBufs& b = ctx->tr;
+  hipStream_t s = ctx->stream;
+  const int nmaps = (ldos ? 1 : 0) + (akw ? 1 : 0);
+  // X (the DFT'd columns, N x n2, ld N) in the slots' Jmn, its x pass through
+  // JU; unfused: |U|² and |X|² (N x n2 doubles each) then share the slots' JU
+  double2* X = b.Jmn;
+  double* W = reinterpret_cast<double*>(b.JU);
+  const int64_t sW = 2 * sA, oWk = (int64_t)N * n2;
+  {
+    Scope sc(ctx, T_SPECTRAL, 0.0);
+    if (akw) dwh::launch_sp_dft(b.U, sA, (int)ctx->model->Lx, (int)ctx->model->Ly, b.JU, sA, X, sA, m, s);
+    if (!fused) {
+      if (ldos) dwh::launch_sp_sqmod(b.U, n2, sA, N, n2, W, sW, m, s);
+      if (akw) dwh::launch_sp_sqmod(X, N, sA, N, n2, W + oWk, sW, m, s);
+    }
+    HIPCHECK(ctx, hipGetLastError());
+  }
+  for (int64_t q0 = 0; q0 < count; q0 += kSpChunk) {
+    const int cnt = (int)std::min<int64_t>(kSpChunk, count - q0);
+    {
+      Scope sc(ctx, T_SPECTRAL, 2.0 * N * (double)n2 * cnt * nmaps * m);
+      dwh::launch_sp_lorentz(b.E, n2, eta, -omega_max, domega, first + q0 * stride, stride, cnt, ctx->d_sp_lam,
+                             kSpChunk, sLam, m, s);
+      if (fused) {
+        if (ldos)
+          dwh::launch_sp_maps(b.U, n2, sA, ctx->d_sp_lam, kSpChunk, sLam, N, cnt, n2, 1.0, ctx->d_sp_out, N, sOut, m, s);
+        if (akw)
+          dwh::launch_sp_maps(X, N, sA, ctx->d_sp_lam, kSpChunk, sLam, N, cnt, n2, 1.0 / N, ctx->d_sp_out + sTile, N,
+                              sOut, m, s);
+      } else {
+        if (ldos)
+          dwh::gemm_d('N', 'T', N, cnt, n2, 1.0, W, N, sW, ctx->d_sp_lam, kSpChunk, sLam, 0.0, ctx->d_sp_out, N, sOut,
+                      m, s);
+        if (akw)
+          dwh::gemm_d('N', 'T', N, cnt, n2, 1.0 / N, W + oWk, N, sW, ctx->d_sp_lam, kSpChunk, sLam, 0.0,
+                      ctx->d_sp_out + sTile, N, sOut, m, s);
+      }
+      HIPCHECK(ctx, hipGetLastError());
+    }
+    const size_t bytes = (size_t)N * cnt * sizeof(double);
+    for (int k = 0; k < m; ++k) {
+      const size_t dst = (size_t)N * q0 + (size_t)N * count * k;
+      if (ldos)
+        HIPCHECK(ctx, hipMemcpyAsync(ldos + dst, ctx->d_sp_out + k * sOut, bytes, hipMemcpyDeviceToHost, s));
+      if (akw)
+        HIPCHECK(ctx, hipMemcpyAsync(akw + dst, ctx->d_sp_out + k * sOut + sTile, bytes, hipMemcpyDeviceToHost, s));
+    }
+  }
+  return eigen_info_check(ctx, m);
+}
+
 }  // namespace
 
 extern "C" {
@@ -928,28 +1034,61 @@ int dwh_measure_transport_deltas(dwh_ctx* ctx, int64_t chain, int64_t nstates, c
   SETTLE(ctx);
   const int N = ctx->d.N;
   const int64_t n2 = 2 * (int64_t)N;
-  for (int64_t e = 0; e < nstates * n2; ++e)
-    if (!std::isfinite(Delta[e].re) || !std::isfinite(Delta[e].im)) return fail(ctx, DWH_ERR_ARG, "non-finite Delta");
-  // staging buffer for the snapshots (grown on demand)
-  if (nstates > ctx->tr_nstage) {
-    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-    drop_alloc(ctx, ctx->d_tr_stage);
-    ctx->d_tr_stage = nullptr;
-    ctx->tr_nstage = 0;
-    if ((rc = dalloc(ctx, &ctx->d_tr_stage, (size_t)nstates * n2))) return rc;
-    ctx->tr_nstage = nstates;
-  }
-  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_tr_stage, Delta, (size_t)nstates * n2 * sizeof(double2),
-                               hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = stage_deltas(ctx, nstates, Delta))) return rc;
   // groups whose three n2 x n2 work matrices fit in 16 GiB, as the batched call
-  const double per = 3.0 * 16.0 * 4.0 * N * (double)N;
-  const int group = std::max(1, std::min((int)nstates, (int)(16.0 * (1 << 30) / per)));
+  const int group = tr_group(ctx, nstates);
   for (int64_t s0 = 0; s0 < nstates; s0 += group) {
     const int m = (int)std::min<int64_t>(group, nstates - s0);
     const TrSrc src{ctx->d_tr_stage + s0 * n2, n2, chain, 0};
     if ((rc = transport_run(ctx, src, m, eta, domega, omega_max, nw, nd, stiffness + s0, dc_cond + s0,
                             sigma ? sigma + (size_t)s0 * nw : nullptr, dos ? dos + (size_t)s0 * nd : nullptr,
                             dos_an ? dos_an + (size_t)s0 * nd : nullptr, ak0 + (size_t)s0 * N)))
+      return rc;
+  }
+  return DWH_OK;
+}
+
+int dwh_spectral_window(double eta, double domega, double omega_max, int64_t first, int64_t count, int64_t stride,
+                        double* omega) {
+#pragma clang fp contract(off)   // start + k·Δω rounded twice, as the device's grid_point
+  int64_t nw = 0, nd = 0;
+  if (int rc = dwh_transport_grid(eta, domega, omega_max, &nw, &nd)) return rc;
+  if (count < 1 || stride < 1) return fail(nullptr, DWH_ERR_ARG, "spectral window: count and stride must be >= 1");
+  if (first < 0 || first >= nd || count - 1 > (nd - 1 - first) / stride)
+    return fail(nullptr, DWH_ERR_ARG, "spectral window leaves the DOS grid of " + std::to_string(nd) + " points");
+  if (omega)
+    for (int64_t q = 0; q < count; ++q) {
+      const double step = domega * (double)(first + q * stride);
+      omega[q] = -omega_max + step;
+    }
+  return DWH_OK;
+}
+
+int dwh_measure_spectral_maps(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta, double eta,
+                              double domega, double omega_max, int64_t first, int64_t count, int64_t stride,
+                              double* ldos, double* akw) {
+  if (!ctx) return fail(nullptr, DWH_ERR_ARG, "NULL context");
+  if (!ldos && !akw) return fail(ctx, DWH_ERR_ARG, "ldos and akw are both NULL");
+  if (chain < 0 || chain >= ctx->d.nc) return fail(ctx, DWH_ERR_ARG, "chain index out of range");
+  if (nstates < 1) return fail(ctx, DWH_ERR_ARG, "nstates must be >= 1");
+  if (!Delta && nstates != 1) return fail(ctx, DWH_ERR_ARG, "nstates must be 1 at the device Delta (Delta == NULL)");
+  if (dwh_spectral_window(eta, domega, omega_max, first, count, stride, nullptr) != DWH_OK)
+    return fail(ctx, DWH_ERR_ARG, g_create_error);
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  SETTLE(ctx);
+  const int N = ctx->d.N;
+  const int64_t n2 = 2 * (int64_t)N;
+  if (!Delta)
+    return spectral_run(ctx, chains_src(ctx, chain), 1, eta, domega, omega_max, first, count, stride, ldos, akw);
+  int rc;
+  if ((rc = stage_deltas(ctx, nstates, Delta))) return rc;
+  const int group = tr_group(ctx, nstates);   // as dwh_measure_transport_deltas
+  for (int64_t s0 = 0; s0 < nstates; s0 += group) {
+    const int m = (int)std::min<int64_t>(group, nstates - s0);
+    const TrSrc src{ctx->d_tr_stage + s0 * n2, n2, chain, 0};
+    const size_t off = (size_t)N * count * s0;
+    if ((rc = spectral_run(ctx, src, m, eta, domega, omega_max, first, count, stride, ldos ? ldos + off : nullptr,
+                           akw ? akw + off : nullptr)))
       return rc;
   }
   return DWH_OK;

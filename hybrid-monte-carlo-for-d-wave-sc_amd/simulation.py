@@ -25,7 +25,7 @@ from datetime import datetime
 import numpy as np
 
 from . import hmc as H
-from .context import transport_grid
+from .context import spectral_window, transport_grid
 
 OBS_HEADER = ("Sweep,Accepted,dH,Energy,Delta_Amp,Delta_Loc,Delta_Glob,S_Delta,Hole_p,Delta_Diff,"
               "Delta_Pair,Delta_LocalPair")
@@ -89,31 +89,57 @@ def write_spectra_header(spec_dir: str, p) -> None:
     np.save(os.path.join(spec_dir, "omega_grid.npy"), p.eta + p.domega * np.arange(n))
 
 
+def write_maps_header(spec_dir: str, p, spectral_maps: dict) -> None:
+    """maps_omega.npy: the frequencies of the spectral-maps window."""
+    os.makedirs(spec_dir, exist_ok=True)
+    np.save(os.path.join(spec_dir, "maps_omega.npy"),
+            spectral_window(p.eta, p.domega, p.omega_max, **_maps_window(spectral_maps)))
+
+
+def _maps_window(spectral_maps: dict) -> dict:
+    """first / count / stride of a run's `spectral_maps` option."""
+    extra = set(spectral_maps) - {"first", "count", "stride"}
+    if extra:
+        raise ValueError(f"spectral_maps: unknown keys {sorted(extra)}")
+    return dict(first=spectral_maps.get("first", 0), count=spectral_maps.get("count"),
+                stride=spectral_maps.get("stride", 1))
+
+
 class SpectraBins:
     """Bin accumulator of src/Simulation.jl:180-220: sums the spectra of
-    bin_size measurements, then writes their mean as group sweep_<i>."""
+    bin_size measurements, then writes their mean as group sweep_<i>.  With
+    spectral maps (add's `maps`: the ldos / akw of that measurement, each
+    (count, Ly, Lx)) the group also holds their bin means, summed the same way."""
 
     def __init__(self):
         self.count = 0
         self.acc = None
+        self.maps = None
 
-    def add(self, spec) -> int:
+    def add(self, spec, maps=None) -> int:
         arrs = [spec.optical_conductivity, spec.dos, spec.dos_AN, spec.A_k_omega0]
         if self.count == 0:
             self.acc = [np.array(a, dtype=np.float64, copy=True) for a in arrs]
+            self.maps = None if maps is None else {k: np.array(maps[k], dtype=np.float64, copy=True)
+                                                   for k in ("ldos", "akw")}
         else:
             for a, b in zip(self.acc, arrs):
                 a += b
+            if self.maps is not None:
+                for k in self.maps:
+                    self.maps[k] += maps[k]
         self.count += 1
         return self.count
 
     def flush(self, spec_dir: str, sweep: int) -> None:
         c = self.count
         oc, dos, dos_an, ak = (a / c for a in self.acc)
+        extra = {} if self.maps is None else {k: v / c for k, v in self.maps.items()}
         np.savez(os.path.join(spec_dir, f"sweep_{sweep}.npz"), opt_cond=oc, dos=dos, dos_AN=dos_an,
-                 A_k0=ak, count=c)
+                 A_k0=ak, count=c, **extra)
         self.count = 0
         self.acc = None
+        self.maps = None
 
 
 class ChainOutput:
@@ -149,10 +175,10 @@ class ChainOutput:
         self.f_obs.write(obs_csv_line(i, acc, dH, obs))
         self.f_obs.flush()
 
-    def transport(self, i, spec, bin_size):
+    def transport(self, i, spec, bin_size, maps=None):
         self.f_trans.write(transport_csv_line(i, spec))
         self.f_trans.flush()
-        if self.bins.add(spec) >= bin_size:
+        if self.bins.add(spec, maps) >= bin_size:
             self.bins.flush(self.spec_dir, i)
 
     def close(self):
@@ -192,11 +218,15 @@ class TransportQueue:
     a batch run as one batched call (dwh_measure_transport_deltas), ~3x the
     throughput of one call per sweep at L = 32.  Rows and bins come out in
     sweep order, each when its batch is measured (batch = 1: right away, as
-    the reference writes them)."""
+    the reference writes them).  spectral_maps (first / count / stride, or
+    None): every measurement also takes LDOS(i, ω) and A(k, ω) on that
+    window (measure_spectral_maps, batched the same way) into the bins."""
 
-    def __init__(self, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int, chain: int = 0):
+    def __init__(self, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int, chain: int = 0,
+                 spectral_maps: dict | None = None):
         self.ctx, self.p, self.out, self.res = ctx, p, out, res
         self.bin_size, self.batch, self.chain = bin_size, max(1, int(batch)), chain
+        self.window = None if spectral_maps is None else _maps_window(spectral_maps)
         self.pending = []            # (sweep, Δ snapshot)
 
     def add(self, sweep: int, Delta):
@@ -213,9 +243,15 @@ class TransportQueue:
         else:
             specs = self.ctx.measure_transport_deltas(np.stack([d for _, d in self.pending]), p.eta, p.domega,
                                                       p.omega_max, chain=self.chain)
-        for (i, _), r in zip(self.pending, specs):
+        maps = None
+        if self.window is not None:
+            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
+            maps = self.ctx.measure_spectral_maps(p.eta, p.domega, p.omega_max, chain=self.chain, deltas=deltas,
+                                                  **self.window)
+        for k, ((i, _), r) in enumerate(zip(self.pending, specs)):
             spec = H.SpectrumResult(**r)
-            self.out.transport(i, spec, self.bin_size)
+            self.out.transport(i, spec, self.bin_size,
+                               None if maps is None else {"ldos": maps["ldos"][k], "akw": maps["akw"][k]})
             self.res.transport.append((i, spec))
         self.pending = []
 
@@ -224,7 +260,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
                    Nt_therm_init: int = 10, Nt_measure: int = 5, measure_transport_freq: int = 1,
                    bin_size: int = 5, verbose: bool = True, rng: np.random.Generator | None = None,
                    device: int = 0, delta_cap: float = 0.0, state: H.SimulationState | None = None,
-                   cache: H.ComputeCache | None = None, transport_batch: int = 1) -> SimulationResult:
+                   cache: H.ComputeCache | None = None, transport_batch: int = 1,
+                   spectral_maps: dict | None = None) -> SimulationResult:
     """src/Simulation.jl:34-236.  Files in out_dir: simulation.log (appended),
     observables.csv, transport.csv (one row per transport measurement, every
     measure_transport_freq sweeps; <= 0 disables), and spectra_bins/ — the
@@ -233,7 +270,13 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
     measurements (opt_cond, dos, dos_AN, A_k0 averaged; count).
     transport_batch > 1 evaluates that many measurement sweeps' transport in
     one batched call (TransportQueue): same rows and bins, written up to
-    transport_batch - 1 sweeps later."""
+    transport_batch - 1 sweeps later.
+    spectral_maps = dict(first=, count=, stride=) (each optional; a window of
+    the DOS grid, FermionContext.measure_spectral_maps): every transport
+    measurement also takes LDOS(i, ω) and A(k, ω) there; each sweep_<i>.npz
+    gains their bin means ldos and akw ((count, Ly, Lx)) and
+    spectra_bins/maps_omega.npy holds the window's frequencies.  None (the
+    default): no maps, the files as without the option."""
     rng = rng if rng is not None else np.random.default_rng()
     out = ChainOutput(out_dir, verbose)
     try:
@@ -247,6 +290,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         H.diagonalize_H_BdG(cache, p)
         if measure_transport_freq > 0:
             write_spectra_header(out.spec_dir, p)
+            if spectral_maps is not None:
+                write_maps_header(out.spec_dir, p, spectral_maps)
         Nt_fin, acc_th = thermalize(cache, p, state, out, n_therm, Nt_therm_init, rng)
 
         dt_meas = H.calc_optimal_dt(p.beta, p.J, p.mass, Nt_measure)
@@ -255,7 +300,7 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         t1 = time.time()
         acc_total = 0
         res = SimulationResult(Nt_fin, acc_th, 0.0)
-        tq = TransportQueue(cache.require(), p, out, res, bin_size, transport_batch)
+        tq = TransportQueue(cache.require(), p, out, res, bin_size, transport_batch, spectral_maps=spectral_maps)
         for i in range(1, n_measure + 1):
             acc, dH = H.hmc_sweep(cache, p, state, Nt=Nt_measure, dt=dt_meas, rng=rng)
             acc_total += int(acc)
@@ -277,7 +322,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
 def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int = 100, n_measure: int = 500,
                           Nt_therm_init: int = 10, Nt_measure: int = 5, measure_transport_freq: int = 1,
                           bin_size: int = 5, verbose: bool = False, device: int = 0,
-                          delta_cap: float = 0.0, transport_batch: int = 1) -> list:
+                          delta_cap: float = 0.0, transport_batch: int = 1,
+                          spectral_maps: dict | None = None) -> list:
     """len(out_dirs) independent run_simulation's (src/Simulation.jl:34-236),
     chain k writing out_dirs[k] and drawing from rngs[k] in the reference's
     order (initialize_state, then per sweep randn(ComplexF64) and rand() only
@@ -293,8 +339,9 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
     backend: on the device the batched context selects one pole set for the
     largest spectral bound over the chains, and a guard trip re-selects it
     for every chain, so dH differs at ~1e-12 and a Metropolis decision can
-    differ)."""
+    differ).  spectral_maps: as run_simulation's, for every chain."""
     K = len(out_dirs)
+    window = None if spectral_maps is None else _maps_window(spectral_maps)
     if len(rngs) != K or K < 1:
         raise ValueError("one rng per output directory")
     outs = [ChainOutput(d, verbose) for d in out_dirs]
@@ -309,6 +356,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
             H.diagonalize_H_BdG(cache, p)
             if measure_transport_freq > 0:
                 write_spectra_header(outs[k].spec_dir, p)
+                if spectral_maps is not None:
+                    write_maps_header(outs[k].spec_dir, p, spectral_maps)
             Nt_fin, acc_th = thermalize(cache, p, st, outs[k], n_therm, Nt_therm_init, rngs[k])
             cache.ctx.close()
             states.append(st)
@@ -326,7 +375,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                 o.tee(f"Settings: Nt={Nt_measure}, dt={round(dt_meas, 5)}")
             t1 = time.time()
             acc_total = np.zeros(K, dtype=np.int64)
-            tqs = [TransportQueue(ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k)
+            tqs = [TransportQueue(ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k,
+                                  spectral_maps=spectral_maps)
                    for k in range(K)] if transport_batch > 1 else None
             for i in range(1, n_measure + 1):
                 noise = np.stack([H.standard_complex_normal(r, (p.N, 2)) for r in rngs])
@@ -349,7 +399,11 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                     results[k].records.append((i, bool(acc[k]), float(dH[k]), obs))
                     if specs is not None:
                         spec = H.SpectrumResult(**specs[k])
-                        outs[k].transport(i, spec, bin_size)
+                        maps = None
+                        if window is not None:
+                            m = ctx.measure_spectral_maps(p.eta, p.domega, p.omega_max, chain=k, **window)
+                            maps = {"ldos": m["ldos"][0], "akw": m["akw"][0]}
+                        outs[k].transport(i, spec, bin_size, maps)
                         results[k].transport.append((i, spec))
                     if i % 10 == 0:
                         outs[k].tee("Meas %d/%d. Acc=%.2f. E=%.4f" % (i, n_measure, acc_total[k] / i,

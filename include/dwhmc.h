@@ -181,7 +181,7 @@ int dwh_stream(dwh_ctx* ctx, void** stream);
  * (bench/profiling).  enable is a bitmask over the timer names below
  * (bit 0 "gj_update", bit 1 "gj_pivot", bit 2 "assemble", bit 3 "contract",
  * bit 4 "step", bit 5 "gj_edge", bit 6 "cr_gemm", bit 7 "cr_inv", bit 8 "cr_inv_side",
- * bit 9 "eig_own", bit 10 "eig_vendor", bit 11 "cr_sparse");
+ * bit 9 "eig_own", bit 10 "eig_vendor", bit 11 "cr_sparse", bit 12 "spectral");
  * 0 disables, -1 times everything. */
 int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
 /* name: "gj_update" (rank-128 paired / rank-64 trailing updates),
@@ -191,7 +191,10 @@ int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
  * the critical path; work = inversion + side-product flops), "cr_sparse" (the
  * sparse level-0 stages: products with the level-0 U / L blocks, work = their
  * sparse flops), "eig_own" / "eig_vendor" (eigensolves by the library's solver /
- * by rocSOLVER, opt-in or fallback; work = matrices), "assemble",
+ * by rocSOLVER, opt-in or fallback; work = matrices), "spectral" (the map
+ * stage of dwh_measure_spectral_maps after its eigensolve: column DFTs,
+ * Lorentzian tables and the two products; work = 2·N·2N·count flops per map
+ * per state), "assemble",
  * "contract", "step"; returns total milliseconds, launches and the
  * algorithmic work summed over launches (fp64 flops; HBM bytes for
  * "assemble"). */
@@ -269,6 +272,46 @@ int dwh_measure_transport_deltas(dwh_ctx* ctx, int64_t chain, int64_t nstates, c
                                  double eta, double domega, double omega_max, double* stiffness,
                                  double* dc_cond, double* sigma, int64_t n_omega, double* dos, double* dos_an,
                                  int64_t n_dos, double* ak0);
+
+/* ---- resolved spectral maps ----------------------------------------------
+ * The site- and momentum-resolved spectra the reference leaves out
+ * [src/Observables.jl:305-307], in its own DOS normalisation.  With E_n, U the
+ * eigenpairs of H_BdG(Δ), u_n(i) = U[i, n] for the particle rows i < N,
+ * L(x) = (1/π) η/(x² + η²) and û_n(k) the unnormalised forward 2-D DFT of u_n
+ * as an Lx x Ly image (site i = x + Lx·y, e^{-2πi(kx·x/Lx + ky·y/Ly)}, the
+ * conventions of A(k, ω=0) above):
+ *   LDOS(i, ω) = Σ_{n<2N} |u_n(i)|² L(ω - E_n)
+ *   A(k, ω)    = (1/N) Σ_{n<2N} |û_n(k)|² L(ω - E_n)
+ * so that (1/N) Σ_i LDOS = (1/N) Σ_k A = dos(ω), and for even Lx, Ly
+ * [A((Lx/2, 0), ω) + A((0, Ly/2), ω)] / 2 = dos_an(ω).
+ * ω runs over a window of the DOS grid -ω_max:Δω:ω_max: the points
+ * first + q·stride, q < count.
+ *
+ * Frequencies of a window of the DOS grid: points first + q*stride, q < count.
+ * Host only.  omega (nullable): count values.  DWH_ERR_ARG if the window
+ * leaves the grid (or count < 1, stride < 1). */
+int dwh_spectral_window(double eta, double domega, double omega_max,
+                        int64_t first, int64_t count, int64_t stride, double* omega);
+
+/* LDOS and A(k, ω) of one chain at the device Δ (Delta == NULL, nstates == 1)
+ * or at nstates pairing fields (the Delta layout of
+ * dwh_measure_transport_deltas, eigensolves batched in the same groups).
+ * ldos / akw: either may be NULL (that map is skipped; both NULL is
+ * DWH_ERR_ARG).  Per state s, column-major N x count:
+ *   ldos[i + N*q + N*count*s],  akw[kx + Lx*ky + N*q + N*count*s].
+ * One eigensolve per state (not shared with a transport call), then two real
+ * fp64 MFMA products against one Lorentzian table (dwhmc_spectral.hip).  The
+ * window is processed in chunks of 1024 frequencies, which bounds the device
+ * workspace per state by 32 KiB·N (table 2N x 1024, two output tiles N x
+ * 1024).  The context's own Δ is not touched.  The products run as |X|²
+ * written out, then the library's real product (the default, also
+ * DWHMC_SPECTRAL_FUSED=0 in the environment); DWHMC_SPECTRAL_FUSED=1 selects
+ * the fused kernel that squares X as it stages it (slower where measured,
+ * kept for A/B). */
+int dwh_measure_spectral_maps(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta,
+                              double eta, double domega, double omega_max,
+                              int64_t first, int64_t count, int64_t stride,
+                              double* ldos, double* akw);
 
 /* ---- assembly read-back (parity tests; not on the hot path) -------------
  * The BdG matrix H_BdG(Δ) exactly as the device assembles it, so tests can

@@ -186,6 +186,35 @@ function measure_transport_and_spectra(cache::GPUCache, p::ModelParameters)
                                    collect(-p.ω_max:p.Δω:p.ω_max), dos, dos_AN, ak)
 end
 
+# The resolved spectra SpectrumResult leaves out (src/Observables.jl:305-307), for
+# the Δ the context holds, on the window first + q·stride (q < count, 0-based
+# points) of the DOS grid -ω_max:Δω:ω_max; count = nothing: to the end of the grid.
+#   ldos[x, y, q] = Σ_n |u_n(i)|² L(ω_q - E_n),         i = x + Lx·y
+#   akw[kx, ky, q] = (1/N) Σ_n |û_n(k)|² L(ω_q - E_n)   (FFTW's forward sign)
+# Returns (ω, ldos, akw); a map switched off comes back as `nothing`.
+function measure_spectral_maps(cache::GPUCache, p::ModelParameters; first::Integer=0,
+                               count::Union{Nothing,Integer}=nothing, stride::Integer=1,
+                               ldos::Bool=true, akw::Bool=true)
+    if count === nothing
+        nw, nd = Ref{Int64}(0), Ref{Int64}(0)
+        check(C_NULL, ccall((:dwh_transport_grid, libdwhmc), Cint,
+                            (Float64, Float64, Float64, Ref{Int64}, Ref{Int64}), p.η, p.Δω, p.ω_max, nw, nd))
+        count = (0 <= first < nd[] && stride >= 1) ? (nd[] - 1 - first) ÷ stride + 1 : 0
+    end
+    ω = zeros(max(count, 0))
+    check(C_NULL, ccall((:dwh_spectral_window, libdwhmc), Cint,
+                        (Float64, Float64, Float64, Int64, Int64, Int64, Ptr{Float64}),
+                        p.η, p.Δω, p.ω_max, first, count, stride, ω))
+    L = ldos ? zeros(p.Lx, p.Ly, count) : nothing
+    A = akw ? zeros(p.Lx, p.Ly, count) : nothing
+    GC.@preserve L A check(cache.ctx, ccall((:dwh_measure_spectral_maps, libdwhmc), Cint,
+                           (Ptr{Cvoid}, Int64, Int64, Ptr{ComplexF64}, Float64, Float64, Float64,
+                            Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+                           cache.ctx, 0, 1, C_NULL, p.η, p.Δω, p.ω_max, first, count, stride,
+                           L === nothing ? C_NULL : pointer(L), A === nothing ? C_NULL : pointer(A)))
+    return ω, L, A
+end
+
 # ---------------------------------------------------------------------------
 # run_simulation on the GPU.  The reference constructs its cache inside the
 # driver (`cache = initialize_cache(p)`, src/Simulation.jl:82), so the driver
