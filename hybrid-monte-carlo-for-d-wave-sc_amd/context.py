@@ -314,8 +314,24 @@ class FermionContext:
         self._c(self._lib.dwh_debug_level0(self._h, int(chain), int(pole), int(bool(refill)), ptr(Mcm), ptr(y)))
         return Mcm.T.copy(), y
 
+    def debug_cr_resolvent(self, chain: int = 0, pole: int = 0) -> dict:
+        """What the CR gathers read for batch item (chain, pole) after a
+        factorisation (dwh_debug_cr_resolvent): G12 (N, 4) = G[i, N + cols[i, s]]
+        (cols -1: unused slot, G12 0), diag (N,) = G[i, i] (G22[i, i] =
+        -conj(diag[i])), lndet = ln|det(H_BdG - i y_pole)|, and the pole
+        heights y and weights c."""
+        P = self.info["npoles"]
+        G12 = np.empty((self.N, 4), dtype=np.complex128)
+        cols = np.empty((self.N, 4), dtype=np.int32)
+        diag = np.empty(self.N, dtype=np.complex128)
+        ld = C.c_double()
+        y, cq = np.empty(P), np.empty(P)
+        self._c(self._lib.dwh_debug_cr_resolvent(self._h, int(chain), int(pole), ptr(G12), ptr(cols), ptr(diag),
+                                                 C.byref(ld), ptr(y), ptr(cq)))
+        return dict(G12=G12, cols=cols, diag=diag, lndet=ld.value, y=y, c=cq)
+
     # -- timing ----------------------------------------------------------
-    TIMERS = ("gj_update", "gj_pivot", "assemble", "contract", "step", "gj_edge", "cr_gemm", "cr_inv",
+    TIMERS =("gj_update", "gj_pivot", "assemble", "contract", "step", "gj_edge", "cr_gemm", "cr_inv",
               "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral")
 
     def timing_enable(self, on=True):
@@ -367,6 +383,41 @@ def spectral_window(eta: float, domega: float, omega_max: float, first: int = 0,
     omega = np.empty(max(count, 0))
     check(lib.dwh_spectral_window(float(eta), float(domega), float(omega_max), first, count, stride, ptr(omega)))
     return omega
+
+
+CR_KINDS = {"inv": 0, "inv0": 1, "gemm": 2, "inv_side": 3}
+
+
+def debug_cr_launch(kind: str, BP: int, pool: np.ndarray, ldpart: np.ndarray, blk=None, dst=None, slot=None,
+                    rblk=None, inv32: bool = True, tasks=None, ts: int = 16, ksplit: int = 1, sg: float = 1.0,
+                    device: int = 0, lib=None):
+    """One launch of the library's CR launchers on a caller-supplied pool
+    (dwh_debug_cr_launch).  pool: (nbatch, nblk, BP // 2, BP) complex top
+    halves; ldpart: (nbatch, nslots); tasks: rows of 16 ints {out, cin, nt, bq,
+    a[4], b[4], r0, r1, c0, c1}.  Returns (pool, ldpart) after the launch;
+    ValueError (no launch) for anything the entry's validation refuses."""
+    lib = _lib.load() if lib is None else lib
+    pool = np.array(pool, dtype=np.complex128, order="C")
+    ld = np.array(ldpart, dtype=np.float64, order="C")
+    if pool.ndim != 4 or ld.ndim != 2 or ld.shape[0] != pool.shape[0]:
+        raise ValueError("pool must be (nbatch, nblk, HP, BP) and ldpart (nbatch, nslots)")
+    nbatch, nblk = pool.shape[:2]
+    if pool.shape[2:] != (int(BP) // 2, int(BP)):
+        raise ValueError("pool blocks must be (BP // 2, BP)")
+
+    def ilist(a):
+        return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+
+    blk, dst, slot, rblk = ilist(blk), ilist(dst), ilist(slot), ilist(rblk)
+    ninv = 0 if blk is None else len(blk)
+    for a in (dst, slot, rblk):
+        if a is not None and len(a) != ninv:
+            raise ValueError("inversion lists must have one length")
+    tk = None if tasks is None else np.ascontiguousarray(np.asarray(tasks, dtype=np.int32).reshape(-1, 16))
+    check(lib.dwh_debug_cr_launch(int(device), CR_KINDS[kind], int(BP), nblk, nbatch, ld.shape[1], ptr(pool),
+                                  ptr(ld), ninv, ptr(blk), ptr(rblk), ptr(dst), ptr(slot), int(bool(inv32)),
+                                  0 if tk is None else len(tk), ptr(tk), int(ts), int(ksplit), float(sg)))
+    return pool, ld
 
 
 def selftest_mfma(device: int = 0) -> int:

@@ -213,8 +213,11 @@ __device__ __forceinline__ double readlane_f64(double x, int lane) {
 // STRIDED: lane l holds columns q, q + 4, q + 8, q + 12 (q = l >> 4) instead
 // of 4q .. 4q + 3 — the MFMA C layout of the transposed tile, so a tile kept
 // transposed in MFMA registers is inverted in place without an LDS transpose.
+// chi: the high dword of c (wave-uniform, a power of two, so its low dword is
+// zero; 1 for ordinary tiles), the constant of the select-free form below; the
+// pivoted row and column come out scaled by c (wave_inv16_dpp).
 template <int P, bool STRIDED = false>
-__device__ __forceinline__ void inv16_step(double2 (&a)[4], double& pprod) {
+__device__ __forceinline__ void inv16_step(double2 (&a)[4], double& pprod, unsigned chi) {
   constexpr int PS = STRIDED ? (P & 3) : (P >> 2), PE = STRIDED ? (P >> 2) : (P & 3);
   const int l = threadIdx.x & 63, r = l & 15, q = l >> 4;
   double2 rowp[4];
@@ -229,12 +232,15 @@ __device__ __forceinline__ void inv16_step(double2 (&a)[4], double& pprod) {
   pprod *= m2;
   const bool prow = (r == P);
   // Select-free form: one update a <- a - f rowp' for every entry.  On the
-  // pivot row colp' = piv - 1, so f = (piv - 1)/piv = 1 - 1/piv and the row
-  // becomes a_p / piv; in column p rowp' = piv + 1, so the column becomes
-  // colp - f (piv + 1) = -colp/piv (1/piv on the pivot row) up to one rounding
-  // of colp - f piv.  Replaces ~12 per-lane selects by two adds.
-  const double2 fi = cmul(make_double2(colp.x - (prow ? 1.0 : 0.0), colp.y), inv);
-  rowp[PE].x += (q == PS) ? 1.0 : 0.0;
+  // pivot row colp' = piv - c, so f = (piv - c)/piv = 1 - c/piv and the row
+  // becomes c a_p / piv; in column p rowp' = piv + c, so the column becomes
+  // colp - f (piv + c) = -c colp/piv (c^2/piv on the pivot row) up to one
+  // rounding of colp - f piv.  Replaces ~12 per-lane selects by two adds.
+  // (c or 0 selected on the high dword alone: one v_cndmask, as with a literal 1.0)
+  const double cr = __builtin_bit_cast(double, (unsigned long long)(prow ? chi : 0u) << 32);
+  const double cc = __builtin_bit_cast(double, (unsigned long long)((q == PS) ? chi : 0u) << 32);
+  const double2 fi = cmul(make_double2(colp.x - cr, colp.y), inv);
+  rowp[PE].x += cc;
   const double2 f = fi;
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) {
@@ -247,16 +253,37 @@ __device__ __forceinline__ void inv16_step(double2 (&a)[4], double& pprod) {
 }
 
 template <bool STRIDED, int... Ps>
-__device__ __forceinline__ void inv16_all(double2 (&a)[4], double& pprod,
+__device__ __forceinline__ void inv16_all(double2 (&a)[4], double& pprod, unsigned chi,
                                           std::integer_sequence<int, Ps...>) {
-  (inv16_step<Ps, STRIDED>(a, pprod), ...);
+  (inv16_step<Ps, STRIDED>(a, pprod, chi), ...);
 }
 
 // returns Π |pivot|^2 of the 16 pivots
+//
+// With c = 1 the select-free pivot step forms the pivot row a_p / piv as
+// a_p - (1 - 1/piv) a_p (and 1/piv itself as piv - (1 - 1/piv)(piv + 1)): for
+// |piv| >> 1 that difference cancels and leaves an absolute error eps |piv|
+// in entries of size 1/|piv| — eps |piv|^2 relative, 3.5 digits at the top
+// poles (|piv| ~ y ~ 60; tests/test_cr_kernels.py).  With c of the pivots'
+// size nothing cancels: every pivoted row and column carries a factor c, the
+// not yet pivoted part (and so every pivot) is what it was, and the 16 steps
+// leave c^2 A^-1.  So a tile whose first pivot is large (|a_00| >= 4) runs
+// with c = 2^e <= |a_00| < 2 c (the diagonal of H - i y and of its Schur
+// complements is of one size) and is scaled back by the exact c^-2; every
+// other tile runs with c = 1: the same steps as before, bit for bit.  c is
+// derived beside the first reciprocal, off the pivot chain.
 template <bool STRIDED = false>
 __device__ __forceinline__ double wave_inv16_dpp(double2 (&a)[4]) {
+  const double p0x = readlane_f64(a[0].x, 0), p0y = readlane_f64(a[0].y, 0);
+  const int ex = __builtin_amdgcn_frexp_exp(fma(p0x, p0x, p0y * p0y));   // |a_00|^2 in [2^(ex-1), 2^ex)
+  const int e = ex >= 5 ? (ex - 1) >> 1 : 0;                              // wave-uniform
   double pprod = 1.0;
-  inv16_all<STRIDED>(a, pprod, std::make_integer_sequence<int, 16>{});
+  inv16_all<STRIDED>(a, pprod, (unsigned)(1023 + e) << 20, std::make_integer_sequence<int, 16>{});
+  if (e != 0) {
+    const double s2 = __builtin_ldexp(1.0, -2 * e);
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) a[jj] = make_double2(a[jj].x * s2, a[jj].y * s2);
+  }
   return pprod;
 }
 

@@ -278,6 +278,33 @@ int choose_algo(int32_t algo_req, int64_t Lx, int64_t Ly, AlgoChoice* out) {
   return DWH_OK;
 }
 
+// The 16 x 16 output tiles of task t — its window rounded out to whole tiles,
+// row-major — appended to *out with the task's operands; keep (nullable): only
+// the tiles tr * ntc + tc it holds.  Returns the number appended.  Shared by
+// the planner's product stages and dwh_debug_cr_launch.
+int cr_task_tiles16(const CrTask& t, int ntc, const std::set<int>* keep, std::vector<CrTile>* out) {
+  const int nk = dwh::cr_task_tiles(t, 16), ct = (t.c1 + 15) / 16 - t.c0 / 16;
+  int kept = 0;
+  for (int k = 0; k < nk; ++k) {
+    const int tr = t.r0 / 16 + k / ct, tc = t.c0 / 16 + k % ct;
+    if (keep && !keep->count(tr * ntc + tc)) continue;
+    dwh::CrTile d{};
+    d.out = t.out;
+    d.cin = t.cin;
+    d.nt = t.nt;
+    d.bq = t.bq;
+    for (int h = 0; h < 4; ++h) {
+      d.a[h] = t.a[h];
+      d.b[h] = t.b[h];
+    }
+    d.tr = tr;
+    d.tc = tc;
+    out->push_back(d);
+    kept++;
+  }
+  return kept;
+}
+
 // Block cyclic reduction of the periodic block-tridiagonal H_BdG - i y (blocks
 // = lattice rows) into stages; restates tools/cr_model.py
 // cr_selected_inverse_top (checked there against dense inverses for Ly = 1 ..
@@ -509,25 +536,8 @@ CrPlan build_cr_plan(int Lx, int Ly, int BP, const std::vector<int>& Dcol, bool 
     st.cfg = {16, 1};
     for (size_t ti = 0; ti < cur_tasks.size(); ++ti) {
       const dwh::CrTask& t = cur_tasks[ti];
-      const int nk = dwh::cr_task_tiles(t, 16), ct = (t.c1 + 15) / 16 - t.c0 / 16;
-      int kept = 0;
-      for (int k = 0; k < nk; ++k) {
-        const int tr = t.r0 / 16 + k / ct, tc = t.c0 / 16 + k % ct;
-        if (cur_keep[ti] && !cur_keep[ti]->count(tr * ntc + tc)) continue;
-        dwh::CrTile d{};
-        d.out = t.out;
-        d.cin = t.cin;
-        d.nt = t.nt;
-        d.bq = t.bq;
-        for (int h = 0; h < 4; ++h) {
-          d.a[h] = t.a[h];
-          d.b[h] = t.b[h];
-        }
-        d.tr = tr;
-        d.tc = tc;
-        pl.tiles16.push_back(d);
-        kept++;
-      }
+      const int nk = dwh::cr_task_tiles(t, 16);
+      const int kept = cr_task_tiles16(t, ntc, cur_keep[ti], &pl.tiles16);
       st.flops += 8.0 * t.nt * BP * (double)(t.r1 - t.r0) * (t.c1 - t.c0) * kept / nk;
       st.maxt32 = std::max(st.maxt32, dwh::cr_task_tiles(t, 32));
       st.maxt16 = std::max(st.maxt16, dwh::cr_task_tiles(t, 16));

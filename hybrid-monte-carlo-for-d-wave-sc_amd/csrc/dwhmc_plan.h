@@ -8,6 +8,7 @@
 // arithmetic: needs no device.  Not part of the public ABI.
 #pragma once
 #include <cstdint>
+#include <set>
 #include <vector>
 
 #include "dwhmc_internal.h"
@@ -75,6 +76,14 @@ SpTaskArrays cr_sparse_task_arrays(const CrPlan& pl, int Lx, int Ly, int BP, con
 void cr_sparse_colvals(const std::vector<int>& colpat, int Lx, int Ly, int BP, const std::vector<int>& hcol,
                        const std::vector<double>& hval, const std::vector<int>& Dcol, const std::vector<int>& Dsrc,
                        std::vector<double2>& colval, std::vector<int>& colsrc);
+// The pieces of a 16 x 16 product stage the planner and the kernel test entry
+// (dwh_debug_cr_launch) share: a task's 16 x 16 tiles (window rounded out to
+// whole tiles, row-major; keep, nullable: only the tiles tr * ntc + tc it
+// holds; returns the number appended), the stage's workgroup count and its
+// dispatch-ordered slots (cr_gemm_slot_wgs x 4 / ksplit of them).
+int cr_task_tiles16(const CrTask& t, int ntc, const std::set<int>* keep, std::vector<CrTile>* out);
+int cr_gemm_slot_wgs(const CrDims& c, int ntl16, const CrGemmCfg& cfg);
+void cr_gemm_slots(const CrDims& c, const CrTile* tl16, int ntl16, const CrGemmCfg& cfg, CrSlot* out);
 // lattice rows per CR block; 0: a lattice row does not fit a supported block
 // (2 Lx > 128), the CR path cannot run this lattice
 int cr_rows_per_block(int64_t Lx, int64_t Ly);

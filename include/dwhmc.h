@@ -338,6 +338,56 @@ int dwh_debug_dense_H(dwh_ctx* ctx, int64_t chain, dwh_c128* H);
 int dwh_debug_qeig(dwh_ctx* ctx, int64_t chain, double* E, double* ms);
 int dwh_debug_level0(dwh_ctx* ctx, int64_t chain, int64_t pole, int32_t refill, dwh_c128* M, double* y);
 
+/* ---- CR kernel and per-pole test entries (not on the step path) -----------
+ * dwh_debug_cr_launch: ONE launch of the library's own cyclic-reduction
+ * launchers on a caller-supplied pool (no context), for kernel contract tests
+ * on synthetic blocks.  pool: nbatch x nblk top halves [A | B] (HP x BP
+ * row-major, HP = BP / 2, BP in {32, 64, 96, 128}: exactly the device pool
+ * layout), copied back after the launch; ldpart: nbatch x nslots, uploaded and
+ * copied back (slots no inversion writes keep their value).  kind:
+ *   DWH_CR_INV       block inversions blk[i] -> dst[i] (dst == blk: in place),
+ *                    ln|det| into ldpart[bi][slot[i]], i < ninv; inv32 selects
+ *                    the one-wave kernel at BP 32 (else the generic one);
+ *   DWH_CR_INV0      the level-0 inversions from static R = A^-1 blocks (BP 32,
+ *                    64, 96), out of place; the entry first forms rblk[i] = R
+ *                    and ldA the way context creation does (the [A | 0] blocks
+ *                    inverted out of place by the DWH_CR_INV launch), so the
+ *                    rblk blocks are scratch the launch overwrites;
+ *   DWH_CR_GEMM      a product stage: out = [cin] + sg sum_h A_h B_h per task on
+ *                    the task's window, tile size ts (16, 32) and K split
+ *                    ksplit (1, 2, 4); ts 16 runs the planner's own tile
+ *                    expansion and slot order;
+ *   DWH_CR_INV_SIDE  the DWH_CR_INV inversions with the tasks as side work (BP
+ *                    64), each task's sign in bit 8 of its bq (set: negative).
+ * tasks: ntasks x 16 int32 {out, cin (-1: none), nt, bq (bit h: B_h Q-form,
+ * else M-form), a[4], b[4], r0, r1, c0, c1}; the output window rows [r0, r1) x
+ * columns [c0, c1) is rounded out to whole ts x ts tiles (side work: 32 x 32)
+ * and the rest of `out` is left untouched.  Every index and size is checked on
+ * the host before anything is launched — block ids < nblk, windows inside
+ * HP x BP, nt in 1..4, ts 32 only where HP % 32 == 0, ksplit 4 only with ts 16,
+ * no task writing a block the launch reads or another task writes, no
+ * inversion writing another's source: DWH_ERR_ARG with the reason in
+ * dwh_last_error(NULL), and no launch. */
+enum { DWH_CR_INV = 0, DWH_CR_INV0 = 1, DWH_CR_GEMM = 2, DWH_CR_INV_SIDE = 3 };
+int dwh_debug_cr_launch(int32_t device, int32_t kind, int32_t BP, int32_t nblk, int32_t nbatch, int32_t nslots,
+                        dwh_c128* pool, double* ldpart, int32_t ninv, const int32_t* blk, const int32_t* rblk,
+                        const int32_t* dst, const int32_t* slot, int32_t inv32, int32_t ntasks,
+                        const int32_t* tasks, int32_t ts, int32_t ksplit, double sg);
+
+/* Per-pole read-back of a CR context after dwh_factorize (or a trajectory):
+ * for batch item (chain, pole), with G = (H_BdG(Δ) - i y_pole)^-1, exactly
+ * what the gathers read from the pool:
+ *   G12[i * 4 + s] = G[i, N + j], j = cols[i * 4 + s], for the (up to 4)
+ *     pairing partners j of site i (the entries the force sums; unused slots:
+ *     cols -1, G12 0); cols nullable;
+ *   diag[i] = G[i, i] as stored: the hole diagonal the trace needs follows
+ *     from the M-form of G, G22[i, i] = G[N + i, N + i] = -conj(diag[i]);
+ *   *lndet = ln|det(H_BdG - i y_pole)| = the sum of the block pivots' logs;
+ *   y, cq (nullable, npoles each): pole heights y_q and weights c_q.
+ * DWH_ERR_STATE on a context of another algorithm or before a factorisation. */
+int dwh_debug_cr_resolvent(dwh_ctx* ctx, int64_t chain, int64_t pole, dwh_c128* G12, int32_t* cols, dwh_c128* diag,
+                           double* lndet, double* y, double* cq);
+
 /* Host-only check of the cyclic-reduction schedule dwh_create builds for an
  * Lx x Ly periodic lattice with nearest-neighbour pairing and nbatch = chains x
  * poles batch items (side / inv0: enable the side-work placement and the
