@@ -92,6 +92,8 @@ SIGNATURES = {
                                                _P]),
     "dwh_spectral_window": (C.c_int, [_D, _D, _D, _I64, _I64, _I64, _P]),
     "dwh_measure_spectral_maps": (C.c_int, [_P, _I64, _I64, _P, _D, _D, _D, _I64, _I64, _I64, _P, _P]),
+    "dwh_measure_current_response": (C.c_int, [_P, _I64, _I64, _P, _I32, _I64, _P, _I64, _P, _P]),
+    "dwh_bench_response_product": (C.c_int, [_P, _I64, _DP]),
     "dwh_debug_dense_H": (C.c_int, [_P, _I64, _P]),
     "dwh_debug_qeig": (C.c_int, [_P, _I64, _P, _P]),
     "dwh_debug_level0": (C.c_int, [_P, _I64, _I64, _I32, _P, _P]),

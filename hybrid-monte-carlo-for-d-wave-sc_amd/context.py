@@ -297,6 +297,36 @@ class FermionContext:
             res["akw"] = out_a
         return res
 
+    def measure_current_response(self, direction="x", q=((0, 1),), n_matsubara: int = 1, chain: int = 0,
+                                 deltas=None) -> dict:
+        """Current response Λ_αα(q, iΩ_l) and the diamagnetic term of
+        direction α = "x" / "y" (or 0 / 1) (dwh_measure_current_response) at
+        the lattice momenta q = 2π (mx/Lx, my/Ly) of the list of (mx, my)
+        (not reduced modulo L) and Ω_l = 2π l/β, l < n_matsubara, at the
+        device Δ of `chain` or at the pairing fields `deltas` ((nstates, N, 2))
+        on its lattice and disorder.  Returns dia (float, or (nstates,) with
+        deltas) and lam ((nq, n_matsubara), or (nstates, nq, n_matsubara));
+        the stiffness of the transverse limit is dia - lam[q, 0]."""
+        if direction not in ("x", "y", 0, 1):
+            raise ValueError("direction must be 'x' or 'y'")
+        d = 0 if direction in ("x", 0) else 1
+        qa = np.ascontiguousarray(np.asarray(q, dtype=np.int64).reshape(-1, 2))
+        nq, nl = qa.shape[0], int(n_matsubara)
+        D, ns = None, 1
+        if deltas is not None:
+            Dl = np.asarray(deltas, dtype=np.complex128)
+            if Dl.ndim != 3 or Dl.shape[1:] != (self.N, 2) or Dl.shape[0] < 1:
+                raise ValueError(f"expected (nstates, {self.N}, 2) pairing fields")
+            ns = Dl.shape[0]
+            D = np.ascontiguousarray(np.transpose(Dl, (0, 2, 1)))
+        dia = np.empty(ns)
+        lam = np.empty((ns, max(nq, 0), max(nl, 0)))
+        self._c(self._lib.dwh_measure_current_response(self._h, int(chain), ns, ptr(D), d, nq, ptr(qa), nl,
+                                                       ptr(dia), ptr(lam)))
+        if deltas is None:
+            return dict(dia=float(dia[0]), lam=lam[0])
+        return dict(dia=dia, lam=lam)
+
     # -- assembly read-back (parity tests) --------------------------------
     def debug_dense_H(self, chain: int = 0) -> np.ndarray:
         """H_BdG(Δ) (2N, 2N) as the eigen/transport path assembles it (dwh_debug_dense_H)."""
@@ -332,7 +362,7 @@ class FermionContext:
 
     # -- timing ----------------------------------------------------------
     TIMERS =("gj_update", "gj_pivot", "assemble", "contract", "step", "gj_edge", "cr_gemm", "cr_inv",
-              "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral")
+              "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral", "response")
 
     def timing_enable(self, on=True):
         """on: True (all timers), False, or an iterable of timer names."""
@@ -350,6 +380,13 @@ class FermionContext:
     def bench_assembly(self, reps: int):
         """dwh_bench_assembly: reps back-to-back assembly launches (timer "assemble")."""
         self._c(self._lib.dwh_bench_assembly(self._h, int(reps)))
+
+    def bench_response_product(self, reps: int) -> float:
+        """dwh_bench_response_product: milliseconds per 2N-cubed complex product
+        (the one measure_current_response runs per momentum), warm, reps launches."""
+        ms = C.c_double()
+        self._c(self._lib.dwh_bench_response_product(self._h, int(reps), C.byref(ms)))
+        return ms.value
 
     def timing_read(self, name: str):
         ms = C.c_double()

@@ -22,14 +22,15 @@ namespace dwh {
 
 enum TimerName {
   T_GJ_UPDATE = 0, T_GJ_PIVOT, T_ASSEMBLE, T_CONTRACT, T_STEP, T_GJ_EDGE, T_CR_GEMM, T_CR_INV, T_CR_INVSIDE,
-  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_COUNT
+  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_COUNT
 };
 inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assemble", "contract",
                                                  "step",      "gj_edge",  "cr_gemm",  "cr_inv",
                                                  "cr_inv_side",
                                                  "eig_own",   "eig_vendor",   // eigensolves (work: matrices)
                                                  "cr_sparse",
-                                                 "spectral"};   // LDOS / A(k, ω) map stage (work: flops)
+                                                 "spectral",    // LDOS / A(k, ω) map stage (work: flops)
+                                                 "response"};   // Λ(q, iΩ) after its eigensolve (work: flops)
 
 enum Algo { ALGO_DENSE = 0, ALGO_CR = 1, ALGO_EIG = 2 };
 
@@ -139,6 +140,16 @@ struct dwh_ctx {
   // and the two maps' output tiles (N x kSpChunk each per state)
   int sp_slots = 0;
   double *d_sp_lam = nullptr, *d_sp_out = nullptr;
+  // current response (dwh_measure_current_response), allocated on first use,
+  // grown on demand and freed where the slot buffers are reallocated: d_rs_ws
+  // holds rs_mats n2 x n2 matrices (JU_q and J_nm(q) of one group of momenta,
+  // at most kRsCapBytes), d_rs_part the per-column pair sums of a group,
+  // d_rs_out dia and Λ of one state, the rest the operator of the call (CSR
+  // pattern, complex values per momentum, the direction's bond neighbours)
+  int64_t rs_mats = 0, rs_npart = 0, rs_nout = 0, rs_nval = 0, rs_ncol = 0, rs_nidx = 0;
+  double2 *d_rs_ws = nullptr, *d_rs_val = nullptr;
+  double *d_rs_part = nullptr, *d_rs_out = nullptr;
+  int *d_rs_col = nullptr, *d_rs_idx = nullptr;   // d_rs_idx: rowptr (N + 1), then nbr (3 N)
   // own eigensolver (dwhmc_eig.hip) workspace for eig_slots matrices: hemv
   // partials, v ping-pong, w, tridiagonal (d, e), tau, compact-WY T blocks and
   // the back-transform's two nb x n products; the n x n work lives in the

@@ -349,6 +349,25 @@ void launch_sp_sqmod(const double2* X, int ldx, int64_t sX, int M, int K, double
 void launch_sp_maps(const double2* X, int ldx, int64_t sX, const double* Lam, int ldq, int64_t sLam, int M, int Q,
                     int K, double scale, double* out, int ldo, int64_t sOut, int m, hipStream_t s);
 
+// Current response Λ_αα(q, iΩ_l) (dwhmc_response.hip), one state at a time,
+// the momenta in groups.
+// Matsubara indices per k_rs_pairs launch (one accumulator each per thread);
+// a longer list re-reads J_nm once per chunk
+constexpr int kRsLChunk = 8;
+// f_n = logistic(-β E_n) and the diamagnetic weight per eigenstate for the
+// bond list nbr (3 x N neighbours, 0-based) with hoppings tb[3] (host)
+void launch_rs_colstats(const double2* U, int N, const double* E, double beta, const double* tb, const int* nbr,
+                        double* f, double* dia, hipStream_t s);
+// JU_q = (Jq ⊕ Jq) U, q < nq: Jq in CSR form (N rows, one pattern, nnz complex
+// values per q at val + q nnz), JU_q at JU + q sJU
+void launch_rs_current(const double2* U, double2* JU, int64_t sJU, int N, const int* rowptr, const int* col,
+                       const double2* val, int nnz, int nq, hipStream_t s);
+// part[(q nl + l) n2 + m] = Σ_n r_nm(l) |J_nm(q)|², l < nl, q < nq (J_nm(q) at Jnm + q sJ)
+void launch_rs_pairs(const double2* Jnm, int64_t sJ, int N, const double* E, const double* f, double beta, int nl,
+                     int nq, double* part, hipStream_t s);
+// out[b] = scale Σ_{k<cnt} in[b cnt + k], b < nout, in a fixed order
+void launch_rs_sum(const double* in, int cnt, int nout, double scale, double* out, hipStream_t s);
+
 // Eigendecomposition leapfrog step (algo eig; U, JU, rho: nc chains of n2 x n2
 // column-major, E: nc x n2): JU = U diag(logistic(-β E)); after rho = JU U^H,
 // P at the bonds, Tr ρ_hh and E_f per chain

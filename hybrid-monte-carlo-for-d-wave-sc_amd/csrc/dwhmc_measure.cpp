@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -33,6 +34,19 @@ int64_t julia_range_len(double start, double step, double stop) {
   const double n = std::nearbyint(r);
   const double k = std::fabs(r - n) < 1e-8 * std::max(1.0, std::fabs(r)) ? n : std::floor(r);
   return k < 0 ? 0 : (int64_t)k + 1;
+}
+
+// The current-response workspace (response_run allocates it on first use)
+// goes where the slot buffers are reallocated: both scale with n2², so a
+// caller that grows the slots gets this memory back first.
+void response_release(dwh_ctx* ctx) {
+  for (void* q : {(void*)ctx->d_rs_ws, (void*)ctx->d_rs_val, (void*)ctx->d_rs_part, (void*)ctx->d_rs_out,
+                  (void*)ctx->d_rs_col, (void*)ctx->d_rs_idx})
+    drop_alloc(ctx, q);
+  ctx->d_rs_ws = ctx->d_rs_val = nullptr;
+  ctx->d_rs_part = ctx->d_rs_out = nullptr;
+  ctx->d_rs_col = ctx->d_rs_idx = nullptr;
+  ctx->rs_mats = ctx->rs_npart = ctx->rs_nout = ctx->rs_nval = ctx->rs_ncol = ctx->rs_nidx = 0;
 }
 
 }  // namespace
@@ -71,6 +85,7 @@ int dwh::transport_prepare(dwh_ctx* ctx, int64_t nw, int64_t nd, int slots) {
                     (void*)b.wan, (void*)b.w0, (void*)b.lam, (void*)b.dc, (void*)ctx->d_tr_offd, (void*)b.ak,
                     (void*)b.scalars, (void*)ctx->d_tr_info})
       drop_alloc(ctx, q);
+    response_release(ctx);
     const size_t m = (size_t)slots;
     if ((rc = dalloc(ctx, &b.U, m * n2 * n2)) || (rc = dalloc(ctx, &b.JU, m * n2 * n2)) ||
         (rc = dalloc(ctx, &b.Jmn, m * n2 * n2)))
@@ -904,6 +919,164 @@ int spectral_run(dwh_ctx* ctx, const TrSrc& src, int m, double eta, double domeg
   return eigen_info_check(ctx, m);
 }
 
+// ---------------------------------------------------------------------------
+// finite-momentum current response (include/dwhmc.h, dwhmc_response.hip)
+// ---------------------------------------------------------------------------
+
+// Cap of the matrix workspace of one group of momenta (JU_q and J_nm(q), two
+// n2 x n2 matrices per momentum); one momentum's pair is always allowed
+constexpr double kRsCapBytes = 2.0 * (1u << 30);
+constexpr int kRsMaxGroup = 64;
+
+// The operator of one call on the host: the particle block Jq of direction
+// dir at every momentum of the list as one CSR pattern (duplicates summed, as
+// build_host_model's x operator) with nnz complex values per momentum, the
+// direction's bond neighbours [3][N] and hoppings.
+struct RsOp {
+  std::vector<int> idx;   // rowptr (N + 1), then nbr (3 N)
+  std::vector<int> col;
+  std::vector<double2> val;
+  double tb[3];
+  int nnz = 0;
+};
+
+void build_response_op(const HostModel& m, int dir, int64_t nq, const int64_t* q, RsOp* op) {
+  const int N = m.N, Lx = (int)m.Lx, Ly = (int)m.Ly;
+  // B_x = (nn +x, t, (1,0)), (nnn +x+y, t', (1,1)), (nnn +x-y, t', (1,-1));
+  // B_y = (nn +y, t, (0,1)), (nnn +x+y, t', (1,1)), (nnn -x+y, t', (-1,1))
+  const int* js[3] = {m.nn.data() + (size_t)(dir == 0 ? 0 : 1) * N, m.nnn.data(),
+                      m.nnn.data() + (size_t)(dir == 0 ? 3 : 1) * N};
+  const double dx[3] = {dir == 0 ? 1.0 : 0.0, 1.0, dir == 0 ? 1.0 : -1.0};
+  const double dy[3] = {dir == 0 ? 0.0 : 1.0, 1.0, dir == 0 ? -1.0 : 1.0};
+  op->tb[0] = m.t;
+  op->tb[1] = op->tb[2] = m.tp;
+  std::vector<std::map<int, int>> rows(N);
+  for (int i = 0; i < N; ++i)
+    for (int b = 0; b < 3; ++b) {
+      rows[i][js[b][i]] = 0;
+      rows[js[b][i]][i] = 0;
+    }
+  op->idx.assign((size_t)4 * N + 1, 0);
+  op->col.clear();
+  for (int r = 0; r < N; ++r) {
+    for (auto& kv : rows[r]) {
+      kv.second = (int)op->col.size();
+      op->col.push_back(kv.first);
+    }
+    op->idx[r + 1] = (int)op->col.size();
+  }
+  for (int b = 0; b < 3; ++b)
+    for (int i = 0; i < N; ++i) op->idx[(size_t)N + 1 + (size_t)b * N + i] = js[b][i];
+  const int nnz = op->nnz = (int)op->col.size();
+  op->val.assign((size_t)nq * nnz, make_double2(0.0, 0.0));
+  const double two_pi = 6.28318530717958647692;
+  for (int64_t k = 0; k < nq; ++k) {
+    const double qx = two_pi * (double)q[2 * k] / Lx, qy = two_pi * (double)q[2 * k + 1] / Ly;
+    double2* v = op->val.data() + (size_t)k * nnz;
+    for (int i = 0; i < N; ++i) {
+      const double x = i % Lx, y = i / Lx;
+      for (int b = 0; b < 3; ++b) {
+        // i t_b φ_b(i), φ_b(i) = exp(-i q·(r_i + δ_b/2))
+        const double a = -(qx * (x + 0.5 * dx[b]) + qy * (y + 0.5 * dy[b]));
+        const double2 w = make_double2(-op->tb[b] * std::sin(a), op->tb[b] * std::cos(a));
+        const int j = js[b][i];
+        double2& p = v[rows[i][j]];
+        p.x += w.x;
+        p.y += w.y;
+        double2& t = v[rows[j][i]];
+        t.x -= w.x;
+        t.y -= w.y;
+      }
+    }
+  }
+}
+
+template <typename T>
+int rs_grow(dwh_ctx* ctx, T** p, int64_t* cap, int64_t need) {
+  if (need <= *cap) return DWH_OK;
+  HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+  drop_alloc(ctx, *p);
+  *p = nullptr;
+  *cap = 0;
+  if (int rc = dalloc(ctx, p, (size_t)need)) return rc;
+  *cap = need;
+  return DWH_OK;
+}
+
+// momenta per group: JU_q and J_nm(q) of a group within kRsCapBytes
+// (DWHMC_RESPONSE_GROUP: a smaller group, for tests of the grouping loop)
+int rs_group(const dwh_ctx* ctx, int64_t nq) {
+  const double n2 = 2.0 * ctx->d.N;
+  int g = (int)std::min<double>(kRsMaxGroup, kRsCapBytes / (2.0 * 16.0 * n2 * n2));
+  if (const char* e = std::getenv("DWHMC_RESPONSE_GROUP")) g = std::min(g, std::atoi(e));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(g, nq));
+}
+
+// the call's workspace (capacities in elements) and its operator on the device
+int response_prepare(dwh_ctx* ctx, const RsOp& op, int64_t nq, int64_t nl) {
+  const int64_t n2 = 2 * (int64_t)ctx->d.N, g = rs_group(ctx, nq);
+  int rc;
+  if ((rc = rs_grow(ctx, &ctx->d_rs_ws, &ctx->rs_mats, 2 * g * n2 * n2)) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_part, &ctx->rs_npart, g * nl * n2)) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_out, &ctx->rs_nout, 1 + nq * nl)) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_val, &ctx->rs_nval, (int64_t)op.val.size())) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_col, &ctx->rs_ncol, (int64_t)op.col.size())) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_idx, &ctx->rs_nidx, (int64_t)op.idx.size())))
+    return rc;
+  hipStream_t s = ctx->stream;
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_rs_val, op.val.data(), op.val.size() * sizeof(double2), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_rs_col, op.col.data(), op.col.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_rs_idx, op.idx.data(), op.idx.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipStreamSynchronize(s));
+  return DWH_OK;
+}
+
+// dia_α and Λ_αα(q, iΩ_l) of the m states of src: one batched eigensolve, then
+// per state the column statistic, U^H once (the slot's Jmn, so every product
+// is 'N','N' as in transport_run), and per group of momenta JU_q, the batched
+// product against the shared U^H (stride 0), the pair sums and their
+// fixed-order reduction.  Every column of J_nm(q) is computed (no
+// particle-hole half sum).  dia: m, lambda: nl x nq per state (host).
+int response_run(dwh_ctx* ctx, const TrSrc& src, int m, const RsOp& op, int64_t nq, int64_t nl, double* dia,
+                 double* lambda) {
+  int rc;
+  if ((rc = transport_prepare(ctx, std::max<int64_t>(ctx->tr_nw, 0), std::max<int64_t>(ctx->tr_nd, 0), m)))
+    return rc;
+  if ((rc = response_prepare(ctx, op, nq, nl))) return rc;   // (transport_prepare may have released it)
+  if ((rc = eigen_solve(ctx, src, m))) return rc;
+  const int N = ctx->d.N, n2 = 2 * N;
+  const int64_t sA = (int64_t)n2 * n2, nout = 1 + nq * nl;
+  const int g = rs_group(ctx, nq);
+  hipStream_t s = ctx->stream;
+  const int *rowptr = ctx->d_rs_idx, *nbr = ctx->d_rs_idx + N + 1;
+  double2 *JU = ctx->d_rs_ws, *Jnm = ctx->d_rs_ws + (int64_t)g * sA;
+  const double2 one = make_double2(1.0, 0.0), zero = make_double2(0.0, 0.0);
+  std::vector<double> out((size_t)m * nout);
+  for (int k = 0; k < m; ++k) {
+    Scope sc(ctx, T_RESPONSE, 8.0 * n2 * (double)n2 * n2 * nq);
+    const dwh::TrBufs b = tr_slot(ctx, k);
+    dwh::launch_rs_colstats(b.U, N, b.E, ctx->beta, op.tb, nbr, b.f, b.dia, s);
+    dwh::launch_rs_sum(b.dia, n2, 1, 1.0 / N, ctx->d_rs_out, s);
+    dwh::launch_tr_conj_transpose(b.U, n2, n2, n2, 0, b.Jmn, n2, 0, 1, s);
+    for (int64_t q0 = 0; q0 < nq; q0 += g) {
+      const int gq = (int)std::min<int64_t>(g, nq - q0);
+      dwh::launch_rs_current(b.U, JU, sA, N, rowptr, ctx->d_rs_col, ctx->d_rs_val + q0 * op.nnz, op.nnz, gq, s);
+      dwh::gemm_z('N', 'N', n2, n2, n2, one, b.Jmn, n2, 0, JU, n2, sA, zero, Jnm, n2, sA, gq, s);
+      dwh::launch_rs_pairs(Jnm, sA, N, b.E, b.f, ctx->beta, (int)nl, gq, ctx->d_rs_part, s);
+      dwh::launch_rs_sum(ctx->d_rs_part, n2, gq * (int)nl, 1.0 / N, ctx->d_rs_out + 1 + q0 * nl, s);
+    }
+    HIPCHECK(ctx, hipGetLastError());
+    HIPCHECK(ctx, hipMemcpyAsync(out.data() + (size_t)k * nout, ctx->d_rs_out, nout * sizeof(double),
+                                 hipMemcpyDeviceToHost, s));
+  }
+  if ((rc = eigen_info_check(ctx, m))) return rc;   // (synchronises)
+  for (int k = 0; k < m; ++k) {
+    dia[k] = out[(size_t)k * nout];
+    std::copy(out.begin() + (size_t)k * nout + 1, out.begin() + (size_t)(k + 1) * nout, lambda + (size_t)k * nq * nl);
+  }
+  return DWH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1091,6 +1264,70 @@ int dwh_measure_spectral_maps(dwh_ctx* ctx, int64_t chain, int64_t nstates, cons
                            akw ? akw + off : nullptr)))
       return rc;
   }
+  return DWH_OK;
+}
+
+int dwh_measure_current_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta,
+                                 int32_t direction, int64_t nq, const int64_t* q, int64_t n_matsubara, double* dia,
+                                 double* lambda) {
+  if (!ctx) return fail(nullptr, DWH_ERR_ARG, "NULL context");
+  if (!q || !dia || !lambda) return fail(ctx, DWH_ERR_ARG, "NULL argument (q, dia or lambda)");
+  if (chain < 0 || chain >= ctx->d.nc) return fail(ctx, DWH_ERR_ARG, "chain index out of range");
+  if (nstates < 1) return fail(ctx, DWH_ERR_ARG, "nstates must be >= 1");
+  if (!Delta && nstates != 1) return fail(ctx, DWH_ERR_ARG, "nstates must be 1 at the device Delta (Delta == NULL)");
+  if (direction != 0 && direction != 1) return fail(ctx, DWH_ERR_ARG, "direction must be 0 (x) or 1 (y)");
+  if (nq < 1) return fail(ctx, DWH_ERR_ARG, "nq must be >= 1");
+  if (n_matsubara < 1) return fail(ctx, DWH_ERR_ARG, "n_matsubara must be >= 1");
+  if (nq > (1 << 24) || n_matsubara > (1 << 24) || nq * n_matsubara > (1 << 24))
+    return fail(ctx, DWH_ERR_ARG, "more than 2^24 (momentum, frequency) points");
+  const HostModel& model = *ctx->model;
+  for (int64_t k = 0; k < nq; ++k)
+    if (std::llabs(q[2 * k]) > model.Lx || std::llabs(q[2 * k + 1]) > model.Ly)
+      return fail(ctx, DWH_ERR_ARG, "momentum index outside |mx| <= Lx, |my| <= Ly");
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  SETTLE(ctx);
+  RsOp op;
+  build_response_op(model, direction, nq, q, &op);
+  if (!Delta) return response_run(ctx, chains_src(ctx, chain), 1, op, nq, n_matsubara, dia, lambda);
+  int rc;
+  if ((rc = stage_deltas(ctx, nstates, Delta))) return rc;
+  const int64_t n2 = 2 * (int64_t)ctx->d.N;
+  const int group = tr_group(ctx, nstates);   // as dwh_measure_transport_deltas
+  for (int64_t s0 = 0; s0 < nstates; s0 += group) {
+    const int m = (int)std::min<int64_t>(group, nstates - s0);
+    const TrSrc src{ctx->d_tr_stage + s0 * n2, n2, chain, 0};
+    if ((rc = response_run(ctx, src, m, op, nq, n_matsubara, dia + s0, lambda + (size_t)s0 * nq * n_matsubara)))
+      return rc;
+  }
+  return DWH_OK;
+}
+
+int dwh_bench_response_product(dwh_ctx* ctx, int64_t reps, double* ms) {
+  if (!ctx || !ms) return fail(ctx, DWH_ERR_ARG, "NULL argument");
+  if (reps < 1 || reps > 1000) return fail(ctx, DWH_ERR_ARG, "reps must be in [1, 1000]");
+  if (ctx->tr_slots < 1) return fail(ctx, DWH_ERR_STATE, "no measurement has run on this context yet");
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  SETTLE(ctx);
+  const int n2 = 2 * ctx->d.N;
+  const int64_t sA = (int64_t)n2 * n2;
+  const dwh::TrBufs& b = ctx->tr;
+  hipStream_t s = ctx->stream;
+  const double2 one = make_double2(1.0, 0.0), zero = make_double2(0.0, 0.0);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPCHECK(ctx, hipEventCreate(&e0));
+  HIPCHECK(ctx, hipEventCreate(&e1));
+  dwh::gemm_z('N', 'N', n2, n2, n2, one, b.Jmn, n2, sA, b.U, n2, sA, zero, b.JU, n2, sA, 1, s);   // warm
+  HIPCHECK(ctx, hipEventRecord(e0, s));
+  for (int64_t r = 0; r < reps; ++r)
+    dwh::gemm_z('N', 'N', n2, n2, n2, one, b.Jmn, n2, sA, b.U, n2, sA, zero, b.JU, n2, sA, 1, s);
+  HIPCHECK(ctx, hipEventRecord(e1, s));
+  HIPCHECK(ctx, hipStreamSynchronize(s));
+  HIPCHECK(ctx, hipGetLastError());
+  float t = 0.f;
+  HIPCHECK(ctx, hipEventElapsedTime(&t, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  *ms = (double)t / (double)reps;
   return DWH_OK;
 }
 

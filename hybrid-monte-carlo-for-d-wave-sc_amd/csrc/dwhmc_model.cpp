@@ -441,6 +441,13 @@ int build_host_model(int64_t Lx, int64_t Ly, double t, double tp, double mu, con
       m.tr_rowptr[r + 1] = (int)m.tr_col.size();
     }
   }
+  m.nn.resize(4 * (size_t)N);
+  m.nnn.resize(4 * (size_t)N);
+  for (int dir = 0; dir < 4; ++dir)
+    for (int i = 0; i < N; ++i) {
+      m.nn[(size_t)dir * N + i] = NN(i, dir);
+      m.nnn[(size_t)dir * N + i] = NNN(i, dir);
+    }
   m.site4.resize(4 * (size_t)N);
   for (int i = 0; i < N; ++i)   // (i, +x), (i, +y), (i - x, +x), (i - y, +y): Delta index = site + N * (bond is +y)
     for (int k = 0; k < 4; ++k) m.site4[4 * i + k] = (k < 2 ? i : NN(i, k)) + N * (k & 1);

@@ -49,6 +49,9 @@ struct HostModel {
   // (duplicates added), as imaginary parts; tr_nbr: those neighbours, [3][N]
   std::vector<int> tr_nbr, tr_rowptr, tr_col;
   std::vector<double> tr_val;
+  // the neighbour tables themselves, 0-based, [dir][N] (the finite-momentum
+  // current operators of either direction are built from them per call)
+  std::vector<int> nn, nnn;
   // site i: the Delta indices of its bonds (i, +x), (i, +y), (i - x, +x), (i - y, +y) (site guard)
   std::vector<int> site4;
 };

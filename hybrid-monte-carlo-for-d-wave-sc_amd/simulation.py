@@ -105,6 +105,28 @@ def _maps_window(spectral_maps: dict) -> dict:
                 stride=spectral_maps.get("stride", 1))
 
 
+def _response_opts(current_response: dict) -> dict:
+    """direction / q / n_matsubara of a run's `current_response` option."""
+    extra = set(current_response) - {"direction", "q", "n_matsubara"}
+    if extra:
+        raise ValueError(f"current_response: unknown keys {sorted(extra)}")
+    q = [(int(mx), int(my)) for mx, my in current_response.get("q", [(0, 1)])]
+    return dict(direction=current_response.get("direction", "x"), q=q,
+                n_matsubara=int(current_response.get("n_matsubara", 1)))
+
+
+def response_csv_header(opts: dict) -> str:
+    """sweep, dia, then Λ in the ABI order (momentum by momentum, l fastest), the
+    columns named by direction, momentum indices and Matsubara index."""
+    a = opts["direction"] if isinstance(opts["direction"], str) else "xy"[opts["direction"]]
+    cols = [f"lam_{a}{a}(mx={mx};my={my};l={l})" for mx, my in opts["q"] for l in range(opts["n_matsubara"])]
+    return ",".join(["sweep", f"dia_{a}"] + cols)
+
+
+def response_csv_line(sweep: int, dia: float, lam) -> str:
+    return ",".join(["%d" % sweep, "%.12e" % dia] + ["%.12e" % v for v in np.asarray(lam).ravel()]) + "\n"
+
+
 class SpectraBins:
     """Bin accumulator of src/Simulation.jl:180-220: sums the spectra of
     bin_size measurements, then writes their mean as group sweep_<i>.  With
@@ -157,6 +179,8 @@ class ChainOutput:
         self.f_obs.write(OBS_HEADER + "\n")
         self.f_trans.write(TRANSPORT_HEADER + "\n")
         self.bins = SpectraBins()
+        self.out_dir = out_dir
+        self.f_resp = None           # current_response.csv, only with the current_response option
 
     def tee(self, msg: str):
         line = f"[{datetime.now().strftime('%Y-%m-%d %H:%M:%S')}] {msg}"
@@ -181,10 +205,20 @@ class ChainOutput:
         if self.bins.add(spec, maps) >= bin_size:
             self.bins.flush(self.spec_dir, i)
 
+    def response(self, i, opts, dia, lam):
+        """One row of current_response.csv (created, with its header, by the first)."""
+        if self.f_resp is None:
+            self.f_resp = open(os.path.join(self.out_dir, "current_response.csv"), "w")
+            self.f_resp.write(response_csv_header(opts) + "\n")
+        self.f_resp.write(response_csv_line(i, dia, lam))
+        self.f_resp.flush()
+
     def close(self):
         self.f_log.close()
         self.f_obs.close()
         self.f_trans.close()
+        if self.f_resp is not None:
+            self.f_resp.close()
 
 
 def thermalize(cache, p, state, out: ChainOutput, n_therm: int, Nt_therm_init: int, rng):
@@ -220,13 +254,17 @@ class TransportQueue:
     sweep order, each when its batch is measured (batch = 1: right away, as
     the reference writes them).  spectral_maps (first / count / stride, or
     None): every measurement also takes LDOS(i, ω) and A(k, ω) on that
-    window (measure_spectral_maps, batched the same way) into the bins."""
+    window (measure_spectral_maps, batched the same way) into the bins.
+    current_response (direction / q / n_matsubara, or None): every
+    measurement also appends its row (sweep, dia, Λ) to current_response.csv
+    (measure_current_response, batched the same way)."""
 
     def __init__(self, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int, chain: int = 0,
-                 spectral_maps: dict | None = None):
+                 spectral_maps: dict | None = None, current_response: dict | None = None):
         self.ctx, self.p, self.out, self.res = ctx, p, out, res
         self.bin_size, self.batch, self.chain = bin_size, max(1, int(batch)), chain
         self.window = None if spectral_maps is None else _maps_window(spectral_maps)
+        self.response = None if current_response is None else _response_opts(current_response)
         self.pending = []            # (sweep, Δ snapshot)
 
     def add(self, sweep: int, Delta):
@@ -248,11 +286,19 @@ class TransportQueue:
             deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
             maps = self.ctx.measure_spectral_maps(p.eta, p.domega, p.omega_max, chain=self.chain, deltas=deltas,
                                                   **self.window)
+        resp = None
+        if self.response is not None:
+            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
+            resp = self.ctx.measure_current_response(chain=self.chain, deltas=deltas, **self.response)
+            if deltas is None:
+                resp = dict(dia=[resp["dia"]], lam=[resp["lam"]])
         for k, ((i, _), r) in enumerate(zip(self.pending, specs)):
             spec = H.SpectrumResult(**r)
             self.out.transport(i, spec, self.bin_size,
                                None if maps is None else {"ldos": maps["ldos"][k], "akw": maps["akw"][k]})
             self.res.transport.append((i, spec))
+            if resp is not None:
+                self.out.response(i, self.response, float(resp["dia"][k]), resp["lam"][k])
         self.pending = []
 
 
@@ -261,7 +307,7 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
                    bin_size: int = 5, verbose: bool = True, rng: np.random.Generator | None = None,
                    device: int = 0, delta_cap: float = 0.0, state: H.SimulationState | None = None,
                    cache: H.ComputeCache | None = None, transport_batch: int = 1,
-                   spectral_maps: dict | None = None) -> SimulationResult:
+                   spectral_maps: dict | None = None, current_response: dict | None = None) -> SimulationResult:
     """src/Simulation.jl:34-236.  Files in out_dir: simulation.log (appended),
     observables.csv, transport.csv (one row per transport measurement, every
     measure_transport_freq sweeps; <= 0 disables), and spectra_bins/ — the
@@ -276,8 +322,15 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
     measurement also takes LDOS(i, ω) and A(k, ω) there; each sweep_<i>.npz
     gains their bin means ldos and akw ((count, Ly, Lx)) and
     spectra_bins/maps_omega.npy holds the window's frequencies.  None (the
-    default): no maps, the files as without the option."""
+    default): no maps, the files as without the option.
+    current_response = dict(direction=, q=, n_matsubara=) (each optional;
+    FermionContext.measure_current_response): every transport measurement
+    also appends one row (sweep, dia, then Λ(q, iΩ_l) momentum by momentum, l
+    fastest) to current_response.csv, whose header names the momenta.  None
+    (the default): no such file, everything else as without the option."""
     rng = rng if rng is not None else np.random.default_rng()
+    if current_response is not None:
+        _response_opts(current_response)
     out = ChainOutput(out_dir, verbose)
     try:
         out.header(p, n_therm, n_measure, measure_transport_freq, bin_size)
@@ -300,7 +353,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         t1 = time.time()
         acc_total = 0
         res = SimulationResult(Nt_fin, acc_th, 0.0)
-        tq = TransportQueue(cache.require(), p, out, res, bin_size, transport_batch, spectral_maps=spectral_maps)
+        tq = TransportQueue(cache.require(), p, out, res, bin_size, transport_batch, spectral_maps=spectral_maps,
+                            current_response=current_response)
         for i in range(1, n_measure + 1):
             acc, dH = H.hmc_sweep(cache, p, state, Nt=Nt_measure, dt=dt_meas, rng=rng)
             acc_total += int(acc)
@@ -323,7 +377,7 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                           Nt_therm_init: int = 10, Nt_measure: int = 5, measure_transport_freq: int = 1,
                           bin_size: int = 5, verbose: bool = False, device: int = 0,
                           delta_cap: float = 0.0, transport_batch: int = 1,
-                          spectral_maps: dict | None = None) -> list:
+                          spectral_maps: dict | None = None, current_response: dict | None = None) -> list:
     """len(out_dirs) independent run_simulation's (src/Simulation.jl:34-236),
     chain k writing out_dirs[k] and drawing from rngs[k] in the reference's
     order (initialize_state, then per sweep randn(ComplexF64) and rand() only
@@ -339,9 +393,11 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
     backend: on the device the batched context selects one pole set for the
     largest spectral bound over the chains, and a guard trip re-selects it
     for every chain, so dH differs at ~1e-12 and a Metropolis decision can
-    differ).  spectral_maps: as run_simulation's, for every chain."""
+    differ).  spectral_maps, current_response: as run_simulation's, for every
+    chain."""
     K = len(out_dirs)
     window = None if spectral_maps is None else _maps_window(spectral_maps)
+    response = None if current_response is None else _response_opts(current_response)
     if len(rngs) != K or K < 1:
         raise ValueError("one rng per output directory")
     outs = [ChainOutput(d, verbose) for d in out_dirs]
@@ -376,7 +432,7 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
             t1 = time.time()
             acc_total = np.zeros(K, dtype=np.int64)
             tqs = [TransportQueue(ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k,
-                                  spectral_maps=spectral_maps)
+                                  spectral_maps=spectral_maps, current_response=current_response)
                    for k in range(K)] if transport_batch > 1 else None
             for i in range(1, n_measure + 1):
                 noise = np.stack([H.standard_complex_normal(r, (p.N, 2)) for r in rngs])
@@ -405,6 +461,9 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                             maps = {"ldos": m["ldos"][0], "akw": m["akw"][0]}
                         outs[k].transport(i, spec, bin_size, maps)
                         results[k].transport.append((i, spec))
+                        if response is not None:
+                            r = ctx.measure_current_response(chain=k, **response)
+                            outs[k].response(i, response, r["dia"], r["lam"])
                     if i % 10 == 0:
                         outs[k].tee("Meas %d/%d. Acc=%.2f. E=%.4f" % (i, n_measure, acc_total[k] / i,
                                                                      obs.total_energy))

@@ -181,7 +181,8 @@ int dwh_stream(dwh_ctx* ctx, void** stream);
  * (bench/profiling).  enable is a bitmask over the timer names below
  * (bit 0 "gj_update", bit 1 "gj_pivot", bit 2 "assemble", bit 3 "contract",
  * bit 4 "step", bit 5 "gj_edge", bit 6 "cr_gemm", bit 7 "cr_inv", bit 8 "cr_inv_side",
- * bit 9 "eig_own", bit 10 "eig_vendor", bit 11 "cr_sparse", bit 12 "spectral");
+ * bit 9 "eig_own", bit 10 "eig_vendor", bit 11 "cr_sparse", bit 12 "spectral",
+ * bit 13 "response");
  * 0 disables, -1 times everything. */
 int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
 /* name: "gj_update" (rank-128 paired / rank-64 trailing updates),
@@ -194,7 +195,9 @@ int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
  * by rocSOLVER, opt-in or fallback; work = matrices), "spectral" (the map
  * stage of dwh_measure_spectral_maps after its eigensolve: column DFTs,
  * Lorentzian tables and the two products; work = 2·N·2N·count flops per map
- * per state), "assemble",
+ * per state), "response" (everything dwh_measure_current_response does after
+ * its eigensolve, one record per state; work = 8·(2N)³ flops per momentum per
+ * state, the J_nm product's), "assemble",
  * "contract", "step"; returns total milliseconds, launches and the
  * algorithmic work summed over launches (fp64 flops; HBM bytes for
  * "assemble"). */
@@ -312,6 +315,57 @@ int dwh_measure_spectral_maps(dwh_ctx* ctx, int64_t chain, int64_t nstates, cons
                               double eta, double domega, double omega_max,
                               int64_t first, int64_t count, int64_t stride,
                               double* ldos, double* akw);
+
+/* ---- finite-momentum current response ------------------------------------
+ * The current-current response Λ_αα(q, iΩ_l) and the diamagnetic term of
+ * direction α (0 = x, 1 = y): the reference's stiffness terms
+ * [src/Observables.jl:340-387], which it takes at q = 0, α = x, Ω = 0 only,
+ * at lattice momenta q = 2π (mx/Lx, my/Ly) and Matsubara frequencies
+ * Ω_l = 2π l/β, in its conventions and normalisation (at q = 0, α = x, l = 0,
+ * dia - Λ is dwh_measure_transport's stiffness).  The limits at Ω = 0: q_x = 0,
+ * q_y -> 0 of Λ_xx (transverse) gives the superfluid stiffness dia - Λ,
+ * q_y = 0, q_x -> 0 (longitudinal) probes gauge invariance.
+ * Site i has x = i mod Lx, y = i div Lx.  Current operator of direction α
+ * with bonds b = (neighbour j_b(i), hopping t_b, bond vector δ_b), duplicate
+ * (row, col) entries summed as in build_current_operator! [:237-283]:
+ *   Jq[i, j_b(i)] += i t_b φ_b(i),  Jq[j_b(i), i] -= i t_b φ_b(i),
+ *   φ_b(i) = exp(-i q·(r_i + δ_b/2)),
+ *   x: (+x, t, (1,0)), (+x+y, t', (1,1)), (+x-y, t', (1,-1))   (the reference's)
+ *   y: (+y, t, (0,1)), (+x+y, t', (1,1)), (-x+y, t', (-1,1)).
+ * The Nambu operator is Jq ⊕ Jq (the hole block equals the particle block at
+ * every q), J(-q) = J(q)^H.  With E_n, U the eigenpairs, f_n = logistic(-β E_n)
+ * and J_nm = (U^H (Jq ⊕ Jq) U)[n, m]:
+ *   Λ_αα(q, l) = (1/N) Σ_{n,m<2N} r_nm(l) |J_nm|²
+ *   l = 0:  r_nm = (f_n - f_m)/(E_m - E_n), β f_n (1 - f_n) where
+ *           |E_m - E_n| < 1e-8 [:370-381]
+ *   l >= 1: r_nm = (f_n - f_m)(E_m - E_n) / ((E_m - E_n)² + Ω_l²)
+ * and dia_α = <-K_α> of [:344-362] with the bond list of α.
+ * Delta == NULL with nstates == 1: the device Δ of `chain`; otherwise nstates
+ * pairing fields (the Delta layout and eigensolve groups of
+ * dwh_measure_transport_deltas); the context's own Δ is not touched.  Works
+ * on contexts of every algorithm.  q: nq pairs (mx, my), |mx| <= Lx,
+ * |my| <= Ly; m is NOT reduced modulo L: the half-bond phase exp(-i q·δ/2) is
+ * not periodic in m, so (mx, my) and (mx + Lx, my) are different operators.
+ * Outputs: dia[s],
+ *   lambda[l + n_matsubara·(k + nq·s)],  l < n_matsubara, k < nq, s < nstates.
+ * One eigensolve per state, then per momentum one 2N-cubed product on the
+ * library's own MFMA kernel around two O(N²) kernels (dwhmc_response.hip),
+ * every sum in a fixed order.  Momenta run in groups whose two work matrices
+ * per momentum stay within 2 GiB (one momentum's pair is always allowed; at
+ * most 64 per group; DWHMC_RESPONSE_GROUP=g in the environment lowers the
+ * group size), allocated on first use.  More than 8 Matsubara frequencies
+ * re-read J_nm once per 8.  DWH_ERR_ARG: direction not 0 / 1, nq < 1,
+ * n_matsubara < 1, a momentum index out of range, NULL q / dia / lambda. */
+int dwh_measure_current_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta,
+                                 int32_t direction, int64_t nq, const int64_t* q, int64_t n_matsubara,
+                                 double* dia, double* lambda);
+/* Bench (tools/bench_current_response.py): the product of one momentum alone,
+ * (2N x 2N)·(2N x 2N) 'N','N' on the measurement buffers of slot 0 as the last
+ * measurement left them, reps times back to back after one warm-up launch,
+ * HIP-event timed; *ms: milliseconds per product.  The yardstick the
+ * "response" timer's per-momentum time is compared against.  Overwrites the
+ * slot's JU.  DWH_ERR_STATE before the context's first measurement. */
+int dwh_bench_response_product(dwh_ctx* ctx, int64_t reps, double* ms);
 
 /* ---- assembly read-back (parity tests; not on the hot path) -------------
  * The BdG matrix H_BdG(Δ) exactly as the device assembles it, so tests can

@@ -215,6 +215,30 @@ function measure_spectral_maps(cache::GPUCache, p::ModelParameters; first::Integ
     return ω, L, A
 end
 
+# The stiffness terms of src/Observables.jl:340-387 away from q = 0, for the Δ
+# the context holds: Λ_αα(q, iΩ_l) of direction α (:x or :y) at the lattice
+# momenta q = 2π (mx/Lx, my/Ly) of `q` (a vector of (mx, my), not reduced
+# modulo L) and Ω_l = 2π l/β, l < n_matsubara, and the diamagnetic term of α.
+# Returns (dia, Λ) with Λ[l + 1, k] for momentum q[k]; dia - Λ[1, k] at
+# q = (0, 1), α = :x is the transverse (superfluid) limit.
+function measure_current_response(cache::GPUCache, p::ModelParameters; direction::Symbol=:x,
+                                  q::AbstractVector=[(0, 1)], n_matsubara::Integer=1)
+    direction in (:x, :y) || throw(ArgumentError("direction must be :x or :y"))
+    nq = length(q)
+    qa = Matrix{Int64}(undef, 2, nq)
+    for (k, (mx, my)) in enumerate(q)
+        qa[1, k], qa[2, k] = mx, my
+    end
+    dia = Ref{Float64}(0.0)
+    Λ = zeros(max(n_matsubara, 0), nq)
+    GC.@preserve qa Λ check(cache.ctx, ccall((:dwh_measure_current_response, libdwhmc), Cint,
+                           (Ptr{Cvoid}, Int64, Int64, Ptr{ComplexF64}, Int32, Int64, Ptr{Int64}, Int64,
+                            Ref{Float64}, Ptr{Float64}),
+                           cache.ctx, 0, 1, C_NULL, direction === :x ? 0 : 1, nq, pointer(qa), n_matsubara,
+                           dia, pointer(Λ)))
+    return dia[], Λ
+end
+
 # ---------------------------------------------------------------------------
 # run_simulation on the GPU.  The reference constructs its cache inside the
 # driver (`cache = initialize_cache(p)`, src/Simulation.jl:82), so the driver
