@@ -5,6 +5,7 @@ Layout:
   _lib.py    ctypes binding of the ABI
   context.py FermionContext: batched device handle
   hmc.py     the reference's hot-path API (ModelParameters ... hmc_sweep)
+  vertices.py sparse one-body vertices for measure_operator_response (host numpy)
   simulation.py run_simulation (src/Simulation.jl): adaptive Nt, log, observables.csv
   replicas.py one-process-per-GPU replica driver (RCCL only gathers observables)
 
@@ -18,6 +19,7 @@ from .hmc import (ComputeCache, ModelParameters, ObservablesResult, SimulationSt
                   measure_transport_and_spectra)
 from .context import FermionContext, debug_cr_launch, selftest_mfma, spectral_window, transport_grid
 from .simulation import AdaptiveNt, SimulationResult, run_simulation, run_simulation_chains
+from . import vertices
 from ._lib import DwhError, SpectrumGuardError, lib_path, load as load_library
 
 __all__ = [
@@ -27,5 +29,5 @@ __all__ = [
     "refresh_momentum", "standard_complex_normal", "update_H_BdG", "FermionContext", "selftest_mfma",
     "DwhError", "SpectrumGuardError", "lib_path", "load_library", "AdaptiveNt", "SimulationResult",
     "run_simulation", "run_simulation_chains", "SpectrumResult", "measure_transport_and_spectra", "transport_grid",
-    "spectral_window", "debug_cr_launch",
+    "spectral_window", "debug_cr_launch", "vertices",
 ]

@@ -327,6 +327,76 @@ class FermionContext:
             return dict(dia=float(dia[0]), lam=lam[0])
         return dict(dia=dia, lam=lam)
 
+    def measure_operator_response(self, ops, spin_sign=None, n_matsubara: int = 1, omega=None, eta=None,
+                                  chain: int = 0, deltas=None) -> dict:
+        """Response of one-body operators O = Σ_ij V_ij (c†_{i↑} c_{j↑} + s
+        c†_{i↓} c_{j↓}) (dwh_measure_operator_response; Nambu matrix
+        V ⊕ (-s V^T)): χ(iΩ_l), l < n_matsubara, in the conventions of
+        measure_current_response's lam, and χ''(ω) on a real-frequency grid
+        in the conventions of σ(ω) without its 1/ω.
+        ops: a tuple (rowptr, col, val) — the CSR pattern shared by all
+        operators (0-based, N rows) with val (nops, nnz) — or a list of
+        operators, each a vertices.Vertex, a COO triple (row, col, val) or a
+        dense (N, N) matrix, which vertices.union_csr puts on one pattern.
+        spin_sign: ±1 per operator (one int for all; None: the Vertex's own).
+        omega: None (no χ''), dict(start=, step=, count=) or (start, step,
+        count): the grid start + j·step, j < count, of either sign; needs
+        eta > 0.  At the device Δ of `chain` or at the pairing fields
+        `deltas` ((nstates, N, 2)).  Returns chi ((nstates,) nops,
+        n_matsubara), chi2 ((nstates,) nops, n_w) and omega (n_w,)."""
+        from . import vertices as vx
+        N = self.N
+        if isinstance(ops, tuple):
+            if len(ops) != 3:
+                raise ValueError("ops: a CSR tuple (rowptr, col, val) or a list of operators")
+            rowptr = np.ascontiguousarray(ops[0], dtype=np.int64).ravel()
+            col = np.ascontiguousarray(ops[1], dtype=np.int64).ravel()
+            val = np.ascontiguousarray(np.atleast_2d(np.asarray(ops[2], dtype=np.complex128)))
+            if len(rowptr) != N + 1 or val.ndim != 2 or val.shape[1] != len(col):
+                raise ValueError(f"ops: rowptr of {N + 1} entries and val (nops, {len(col)}) expected")
+        else:
+            ops = list(ops)
+            if not ops:
+                raise ValueError("ops is empty")
+            if spin_sign is None:
+                if not all(isinstance(o, vx.Vertex) for o in ops):
+                    raise ValueError("spin_sign is needed unless every operator is a vertices.Vertex")
+                spin_sign = [o.spin_sign for o in ops]
+            rowptr, col, val = vx.union_csr(ops, N)
+        nops, nnz = val.shape
+        if spin_sign is None:
+            raise ValueError("spin_sign is needed with a CSR tuple")
+        sg = np.ascontiguousarray(np.broadcast_to(np.asarray(spin_sign, dtype=np.int32), (nops,)))
+        nl = int(n_matsubara)
+        if omega is None:
+            w0, dw, nw = 0.0, 0.0, 0
+        else:
+            if isinstance(omega, dict):
+                extra = set(omega) - {"start", "step", "count"}
+                if extra:
+                    raise ValueError(f"omega: unknown keys {sorted(extra)}")
+                omega = (omega["start"], omega["step"], omega["count"])
+            w0, dw, nw = float(omega[0]), float(omega[1]), int(omega[2])
+            if eta is None:
+                raise ValueError("eta is needed with omega")
+        D, ns = None, 1
+        if deltas is not None:
+            Dl = np.asarray(deltas, dtype=np.complex128)
+            if Dl.ndim != 3 or Dl.shape[1:] != (N, 2) or Dl.shape[0] < 1:
+                raise ValueError(f"expected (nstates, {N}, 2) pairing fields")
+            ns = Dl.shape[0]
+            D = np.ascontiguousarray(np.transpose(Dl, (0, 2, 1)))
+        chi = np.empty((ns, nops, max(nl, 0)))
+        chi2 = np.empty((ns, nops, max(nw, 0)))
+        self._c(self._lib.dwh_measure_operator_response(
+            self._h, int(chain), ns, ptr(D), nops, ptr(rowptr), ptr(col), nnz, ptr(val), ptr(sg), nl,
+            ptr(chi) if nl > 0 else None, 0.0 if eta is None else float(eta), w0, dw, nw,
+            ptr(chi2) if nw > 0 else None))
+        grid = w0 + dw * np.arange(max(nw, 0))
+        if deltas is None:
+            return dict(chi=chi[0], chi2=chi2[0], omega=grid)
+        return dict(chi=chi, chi2=chi2, omega=grid)
+
     # -- assembly read-back (parity tests) --------------------------------
     def debug_dense_H(self, chain: int = 0) -> np.ndarray:
         """H_BdG(Δ) (2N, 2N) as the eigen/transport path assembles it (dwh_debug_dense_H)."""
@@ -362,7 +432,7 @@ class FermionContext:
 
     # -- timing ----------------------------------------------------------
     TIMERS =("gj_update", "gj_pivot", "assemble", "contract", "step", "gj_edge", "cr_gemm", "cr_inv",
-              "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral", "response")
+              "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral", "response", "operator")
 
     def timing_enable(self, on=True):
         """on: True (all timers), False, or an iterable of timer names."""

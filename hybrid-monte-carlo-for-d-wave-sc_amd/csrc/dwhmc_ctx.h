@@ -22,7 +22,7 @@ namespace dwh {
 
 enum TimerName {
   T_GJ_UPDATE = 0, T_GJ_PIVOT, T_ASSEMBLE, T_CONTRACT, T_STEP, T_GJ_EDGE, T_CR_GEMM, T_CR_INV, T_CR_INVSIDE,
-  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_COUNT
+  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_OPERATOR, T_COUNT
 };
 inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assemble", "contract",
                                                  "step",      "gj_edge",  "cr_gemm",  "cr_inv",
@@ -30,7 +30,8 @@ inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assem
                                                  "eig_own",   "eig_vendor",   // eigensolves (work: matrices)
                                                  "cr_sparse",
                                                  "spectral",    // LDOS / A(k, ω) map stage (work: flops)
-                                                 "response"};   // Λ(q, iΩ) after its eigensolve (work: flops)
+                                                 "response",    // Λ(q, iΩ) after its eigensolve (work: flops)
+                                                 "operator"};   // χ(iΩ), χ''(ω) of sparse vertices after their eigensolve (work: flops)
 
 enum Algo { ALGO_DENSE = 0, ALGO_CR = 1, ALGO_EIG = 2 };
 
@@ -150,6 +151,13 @@ struct dwh_ctx {
   double2 *d_rs_ws = nullptr, *d_rs_val = nullptr;
   double *d_rs_part = nullptr, *d_rs_out = nullptr;
   int *d_rs_col = nullptr, *d_rs_idx = nullptr;   // d_rs_idx: rowptr (N + 1), then nbr (3 N)
+  // operator response (dwh_measure_operator_response): shares the buffers
+  // above (d_rs_ws: Ṽ U and V_nm of one group of operators; d_rs_part; d_rs_out:
+  // χ then χ'' of one state; d_rs_val / d_rs_col / d_rs_idx: the 2N-row CSR of
+  // the call); d_op_part holds the χ'' partials of a group (operators x column
+  // chunks x frequencies), released with them
+  int64_t op_npart = 0;
+  double* d_op_part = nullptr;
   // own eigensolver (dwhmc_eig.hip) workspace for eig_slots matrices: hemv
   // partials, v ping-pong, w, tridiagonal (d, e), tau, compact-WY T blocks and
   // the back-transform's two nb x n products; the n x n work lives in the

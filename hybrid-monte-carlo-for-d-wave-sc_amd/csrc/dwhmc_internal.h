@@ -368,6 +368,23 @@ void launch_rs_pairs(const double2* Jnm, int64_t sJ, int N, const double* E, con
 // out[b] = scale Σ_{k<cnt} in[b cnt + k], b < nout, in a fixed order
 void launch_rs_sum(const double* in, int cnt, int nout, double scale, double* out, hipStream_t s);
 
+// Response of a one-body operator (dwhmc_operator.hip), one state at a time,
+// the operators in groups; the Matsubara sums are launch_rs_pairs / launch_rs_sum.
+// Most column chunks of the χ'' partials (one partial per chunk, ω and operator)
+constexpr int kOpSpecChunks = 512;
+int op_spec_chunks(int N);   // chunks in use at this N (rows of the partial buffer per operator, each nw long)
+// f_n = logistic(-β E_n), n < 2N
+void launch_op_fermi(const double* E, int N, double beta, double* f, hipStream_t s);
+// VU_k = Ṽ_k U, k < nops: Ṽ in CSR form (2N rows, columns < 2N, one pattern, nz
+// complex values per operator at val + k nz), VU_k at VU + k sVU
+void launch_op_apply(const double2* U, double2* VU, int64_t sVU, int N, const int* rowptr, const int* col,
+                     const double2* val, int nz, int nops, hipStream_t s);
+// out[j + nw k] = (η/N) Σ_{n,m} (f_n - f_m) |V_nm(k)|² / ((ω_j - (E_m - E_n))² + η²),
+// ω_j = w_start + j w_step, j < nw, k < nops (V_nm(k) at Vnm + k sV); part:
+// nops x op_spec_chunks(N) x nw
+void launch_op_spec(const double2* Vnm, int64_t sV, int N, const double* E, const double* f, double eta,
+                    double w_start, double w_step, int nw, int nops, double* part, double* out, hipStream_t s);
+
 // Eigendecomposition leapfrog step (algo eig; U, JU, rho: nc chains of n2 x n2
 // column-major, E: nc x n2): JU = U diag(logistic(-β E)); after rho = JU U^H,
 // P at the bonds, Tr ρ_hh and E_f per chain

@@ -38,15 +38,16 @@ int64_t julia_range_len(double start, double step, double stop) {
 
 // The current-response workspace (response_run allocates it on first use)
 // goes where the slot buffers are reallocated: both scale with n2², so a
-// caller that grows the slots gets this memory back first.
+// caller that grows the slots gets this memory back first.  The operator
+// response (operator_run) works in the same buffers plus its χ'' partials.
 void response_release(dwh_ctx* ctx) {
   for (void* q : {(void*)ctx->d_rs_ws, (void*)ctx->d_rs_val, (void*)ctx->d_rs_part, (void*)ctx->d_rs_out,
-                  (void*)ctx->d_rs_col, (void*)ctx->d_rs_idx})
+                  (void*)ctx->d_rs_col, (void*)ctx->d_rs_idx, (void*)ctx->d_op_part})
     drop_alloc(ctx, q);
   ctx->d_rs_ws = ctx->d_rs_val = nullptr;
-  ctx->d_rs_part = ctx->d_rs_out = nullptr;
+  ctx->d_rs_part = ctx->d_rs_out = ctx->d_op_part = nullptr;
   ctx->d_rs_col = ctx->d_rs_idx = nullptr;
-  ctx->rs_mats = ctx->rs_npart = ctx->rs_nout = ctx->rs_nval = ctx->rs_ncol = ctx->rs_nidx = 0;
+  ctx->rs_mats = ctx->rs_npart = ctx->rs_nout = ctx->rs_nval = ctx->rs_ncol = ctx->rs_nidx = ctx->op_npart = 0;
 }
 
 }  // namespace
@@ -1077,6 +1078,166 @@ int response_run(dwh_ctx* ctx, const TrSrc& src, int m, const RsOp& op, int64_t 
   return DWH_OK;
 }
 
+// ---------------------------------------------------------------------------
+// response of a one-body operator (include/dwhmc.h, dwhmc_operator.hip)
+// ---------------------------------------------------------------------------
+
+// The operators of one call on the host: Ṽ_k = V_k ⊕ (-s_k V_k^T) as one CSR
+// pattern with n2 = 2N rows and columns in [0, 2N) — rows < N hold V, row
+// N + j holds -s V[i, j] at column N + i — duplicates summed, columns
+// ascending inside a row, nz complex values per operator.
+struct OpNambu {
+  std::vector<int> rowptr, col;
+  std::vector<double2> val;
+  int nz = 0;
+};
+
+// validates the caller's CSR and builds the above; ctx may be NULL (the text
+// then goes where dwh_last_error(NULL) reads it)
+int build_operator_nambu(dwh_ctx* ctx, int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col,
+                         int64_t nnz, const dwh_c128* val, const int32_t* spin_sign, OpNambu* op) {
+  if (N < 1 || N > (1 << 24)) return fail(ctx, DWH_ERR_ARG, "operator: N must be in [1, 2^24]");
+  if (nops < 1 || nnz < 1) return fail(ctx, DWH_ERR_ARG, "operator: nops and nnz must be >= 1");
+  if (nops > (1 << 16) || nnz > (1 << 28) || nops * nnz > (1ll << 29))
+    return fail(ctx, DWH_ERR_ARG, "operator: more than 2^16 operators or 2^28 entries (2^29 values)");
+  if (!rowptr || !col || !val || !spin_sign)
+    return fail(ctx, DWH_ERR_ARG, "NULL argument (rowptr, col, val or spin_sign)");
+  if (rowptr[0] != 0 || rowptr[N] != nnz)
+    return fail(ctx, DWH_ERR_ARG, "operator: rowptr must start at 0 and end at nnz");
+  for (int64_t r = 0; r < N; ++r)
+    if (rowptr[r + 1] < rowptr[r]) return fail(ctx, DWH_ERR_ARG, "operator: rowptr decreases at row " + std::to_string(r));
+  for (int64_t e = 0; e < nnz; ++e)
+    if (col[e] < 0 || col[e] >= N)
+      return fail(ctx, DWH_ERR_ARG, "operator: column " + std::to_string(col[e]) + " outside [0, N)");
+  for (int64_t k = 0; k < nops; ++k)
+    if (spin_sign[k] != 1 && spin_sign[k] != -1)
+      return fail(ctx, DWH_ERR_ARG, "operator: spin_sign must be +1 or -1");
+  const int n = (int)N;
+  // pattern: per row the distinct columns in ascending order -> slot
+  std::vector<std::map<int, int>> rows((size_t)2 * n);
+  for (int i = 0; i < n; ++i)
+    for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+      const int j = (int)col[e];
+      rows[i][j] = 0;
+      rows[(size_t)n + j][n + i] = 0;
+    }
+  op->rowptr.assign((size_t)2 * n + 1, 0);
+  op->col.clear();
+  for (int r = 0; r < 2 * n; ++r) {
+    for (auto& kv : rows[r]) {
+      kv.second = (int)op->col.size();
+      op->col.push_back(kv.first);
+    }
+    op->rowptr[r + 1] = (int)op->col.size();
+  }
+  const int nz = op->nz = (int)op->col.size();
+  op->val.assign((size_t)nops * nz, make_double2(0.0, 0.0));
+  for (int64_t k = 0; k < nops; ++k) {
+    const dwh_c128* v = val + (size_t)k * nnz;
+    double2* o = op->val.data() + (size_t)k * nz;
+    const double hs = -(double)spin_sign[k];
+    for (int i = 0; i < n; ++i)
+      for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+        const int j = (int)col[e];
+        double2& p = o[rows[i][j]];
+        p.x += v[e].re;
+        p.y += v[e].im;
+        double2& h = o[rows[(size_t)n + j][n + i]];
+        h.x += hs * v[e].re;
+        h.y += hs * v[e].im;
+      }
+  }
+  return DWH_OK;
+}
+
+// counts and grid of a call, shared by the device entry's checks
+int operator_args(dwh_ctx* ctx, int64_t nops, int64_t nl, const double* chi, double eta, double w_start,
+                  double w_step, int64_t nw, const double* chi2) {
+  if (nl < 0 || nw < 0) return fail(ctx, DWH_ERR_ARG, "n_matsubara and n_w must be >= 0");
+  if (nl == 0 && nw == 0) return fail(ctx, DWH_ERR_ARG, "n_matsubara and n_w are both 0");
+  if ((nl > 0 && !chi) || (nw > 0 && !chi2)) return fail(ctx, DWH_ERR_ARG, "NULL output (chi or chi2)");
+  if (nops > (1 << 16) || nl > (1 << 24) || nw > (1 << 24) || nops * nl > (1 << 24) || nops * nw > (1 << 26))
+    return fail(ctx, DWH_ERR_ARG, "more than 2^24 (operator, Matsubara) or 2^26 (operator, frequency) points");
+  if (nw > 0) {
+    if (!std::isfinite(eta) || !std::isfinite(w_start) || !std::isfinite(w_step))
+      return fail(ctx, DWH_ERR_ARG, "eta, w_start and w_step must be finite");
+    if (!(eta > 0)) return fail(ctx, DWH_ERR_ARG, "eta must be > 0");
+  }
+  return DWH_OK;
+}
+
+// the call's workspace (capacities in elements) and its operators on the
+// device: the buffers of the current response (which uploads its own operator
+// on every call) and the χ'' partials
+int operator_prepare(dwh_ctx* ctx, const OpNambu& op, int64_t nops, int64_t nl, int64_t nw) {
+  const int64_t n2 = 2 * (int64_t)ctx->d.N, g = rs_group(ctx, nops);
+  int rc;
+  if ((rc = rs_grow(ctx, &ctx->d_rs_ws, &ctx->rs_mats, 2 * g * n2 * n2)) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_part, &ctx->rs_npart, g * nl * n2)) ||
+      (rc = rs_grow(ctx, &ctx->d_op_part, &ctx->op_npart, g * dwh::op_spec_chunks(ctx->d.N) * nw)) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_out, &ctx->rs_nout, nops * (nl + nw))) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_val, &ctx->rs_nval, (int64_t)op.val.size())) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_col, &ctx->rs_ncol, (int64_t)op.col.size())) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_idx, &ctx->rs_nidx, (int64_t)op.rowptr.size())))
+    return rc;
+  hipStream_t s = ctx->stream;
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_rs_val, op.val.data(), op.val.size() * sizeof(double2), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_rs_col, op.col.data(), op.col.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_rs_idx, op.rowptr.data(), op.rowptr.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipStreamSynchronize(s));
+  return DWH_OK;
+}
+
+// χ(l) and χ''(ω_j) of the nops operators at the m states of src: one batched
+// eigensolve, then per state f_n and U^H once (the slot's Jmn, as
+// response_run) and per group of operators Ṽ U, the batched product against
+// the shared U^H (stride 0), the Matsubara pair sums with their fixed-order
+// reduction and the χ'' kernels.  chi: nl x nops, chi2: nw x nops per state (host).
+int operator_run(dwh_ctx* ctx, const TrSrc& src, int m, const OpNambu& op, int64_t nops, int64_t nl, double eta,
+                 double w_start, double w_step, int64_t nw, double* chi, double* chi2) {
+  int rc;
+  if ((rc = transport_prepare(ctx, std::max<int64_t>(ctx->tr_nw, 0), std::max<int64_t>(ctx->tr_nd, 0), m)))
+    return rc;
+  if ((rc = operator_prepare(ctx, op, nops, nl, nw))) return rc;   // (transport_prepare may have released it)
+  if ((rc = eigen_solve(ctx, src, m))) return rc;
+  const int N = ctx->d.N, n2 = 2 * N;
+  const int64_t sA = (int64_t)n2 * n2, nout = nops * (nl + nw);
+  const int g = rs_group(ctx, nops);
+  hipStream_t s = ctx->stream;
+  double2 *VU = ctx->d_rs_ws, *Vnm = ctx->d_rs_ws + (int64_t)g * sA;
+  double *d_chi = ctx->d_rs_out, *d_chi2 = ctx->d_rs_out + nops * nl;
+  const double2 one = make_double2(1.0, 0.0), zero = make_double2(0.0, 0.0);
+  std::vector<double> out((size_t)m * nout);
+  for (int k = 0; k < m; ++k) {
+    Scope sc(ctx, T_OPERATOR, 8.0 * n2 * (double)n2 * n2 * nops);
+    const dwh::TrBufs b = tr_slot(ctx, k);
+    dwh::launch_op_fermi(b.E, N, ctx->beta, b.f, s);
+    dwh::launch_tr_conj_transpose(b.U, n2, n2, n2, 0, b.Jmn, n2, 0, 1, s);
+    for (int64_t k0 = 0; k0 < nops; k0 += g) {
+      const int gk = (int)std::min<int64_t>(g, nops - k0);
+      dwh::launch_op_apply(b.U, VU, sA, N, ctx->d_rs_idx, ctx->d_rs_col, ctx->d_rs_val + k0 * op.nz, op.nz, gk, s);
+      dwh::gemm_z('N', 'N', n2, n2, n2, one, b.Jmn, n2, 0, VU, n2, sA, zero, Vnm, n2, sA, gk, s);
+      if (nl > 0) {
+        dwh::launch_rs_pairs(Vnm, sA, N, b.E, b.f, ctx->beta, (int)nl, gk, ctx->d_rs_part, s);
+        dwh::launch_rs_sum(ctx->d_rs_part, n2, gk * (int)nl, 1.0 / N, d_chi + k0 * nl, s);
+      }
+      if (nw > 0)
+        dwh::launch_op_spec(Vnm, sA, N, b.E, b.f, eta, w_start, w_step, (int)nw, gk, ctx->d_op_part,
+                            d_chi2 + k0 * nw, s);
+    }
+    HIPCHECK(ctx, hipGetLastError());
+    HIPCHECK(ctx, hipMemcpyAsync(out.data() + (size_t)k * nout, ctx->d_rs_out, nout * sizeof(double),
+                                 hipMemcpyDeviceToHost, s));
+  }
+  if ((rc = eigen_info_check(ctx, m))) return rc;   // (synchronises)
+  for (int k = 0; k < m; ++k) {
+    const double* o = out.data() + (size_t)k * nout;
+    if (nl > 0) std::copy(o, o + nops * nl, chi + (size_t)k * nops * nl);
+    if (nw > 0) std::copy(o + nops * nl, o + nout, chi2 + (size_t)k * nops * nw);
+  }
+  return DWH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1299,6 +1460,53 @@ int dwh_measure_current_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, c
     if ((rc = response_run(ctx, src, m, op, nq, n_matsubara, dia + s0, lambda + (size_t)s0 * nq * n_matsubara)))
       return rc;
   }
+  return DWH_OK;
+}
+
+int dwh_measure_operator_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta,
+                                  int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
+                                  const dwh_c128* val, const int32_t* spin_sign, int64_t n_matsubara, double* chi,
+                                  double eta, double w_start, double w_step, int64_t n_w, double* chi2) {
+  if (!ctx) return fail(nullptr, DWH_ERR_ARG, "NULL context");
+  if (chain < 0 || chain >= ctx->d.nc) return fail(ctx, DWH_ERR_ARG, "chain index out of range");
+  if (nstates < 1) return fail(ctx, DWH_ERR_ARG, "nstates must be >= 1");
+  if (!Delta && nstates != 1) return fail(ctx, DWH_ERR_ARG, "nstates must be 1 at the device Delta (Delta == NULL)");
+  int rc;
+  OpNambu op;
+  if (nops < 1 || nnz < 1) return fail(ctx, DWH_ERR_ARG, "operator: nops and nnz must be >= 1");
+  if ((rc = operator_args(ctx, nops, n_matsubara, chi, eta, w_start, w_step, n_w, chi2))) return rc;
+  if ((rc = build_operator_nambu(ctx, ctx->d.N, nops, rowptr, col, nnz, val, spin_sign, &op))) return rc;
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  SETTLE(ctx);
+  if (!Delta)
+    return operator_run(ctx, chains_src(ctx, chain), 1, op, nops, n_matsubara, eta, w_start, w_step, n_w, chi, chi2);
+  if ((rc = stage_deltas(ctx, nstates, Delta))) return rc;
+  const int64_t n2 = 2 * (int64_t)ctx->d.N;
+  const int group = tr_group(ctx, nstates);   // as dwh_measure_transport_deltas
+  for (int64_t s0 = 0; s0 < nstates; s0 += group) {
+    const int m = (int)std::min<int64_t>(group, nstates - s0);
+    const TrSrc src{ctx->d_tr_stage + s0 * n2, n2, chain, 0};
+    if ((rc = operator_run(ctx, src, m, op, nops, n_matsubara, eta, w_start, w_step, n_w,
+                           chi ? chi + (size_t)s0 * nops * n_matsubara : nullptr,
+                           chi2 ? chi2 + (size_t)s0 * nops * n_w : nullptr)))
+      return rc;
+  }
+  return DWH_OK;
+}
+
+int dwh_debug_operator_nambu(int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
+                             const dwh_c128* val, const int32_t* spin_sign, dwh_c128* out) {
+  if (!out) return fail(nullptr, DWH_ERR_ARG, "NULL argument (out)");
+  OpNambu op;
+  if (int rc = build_operator_nambu(nullptr, N, nops, rowptr, col, nnz, val, spin_sign, &op)) return rc;
+  const size_t n2 = 2 * (size_t)N;
+  std::fill(out, out + (size_t)nops * n2 * n2, dwh_c128{0.0, 0.0});
+  for (int64_t k = 0; k < nops; ++k)
+    for (size_t r = 0; r < n2; ++r)
+      for (int e = op.rowptr[r]; e < op.rowptr[r + 1]; ++e) {
+        const double2 v = op.val[(size_t)k * op.nz + e];
+        out[(size_t)k * n2 * n2 + r + (size_t)op.col[e] * n2] = dwh_c128{v.x, v.y};
+      }
   return DWH_OK;
 }
 

@@ -25,6 +25,7 @@ from datetime import datetime
 import numpy as np
 
 from . import hmc as H
+from . import vertices as VX
 from .context import spectral_window, transport_grid
 
 OBS_HEADER = ("Sweep,Accepted,dH,Energy,Delta_Amp,Delta_Loc,Delta_Glob,S_Delta,Hole_p,Delta_Diff,"
@@ -127,11 +128,55 @@ def response_csv_line(sweep: int, dia: float, lam) -> str:
     return ",".join(["%d" % sweep, "%.12e" % dia] + ["%.12e" % v for v in np.asarray(lam).ravel()]) + "\n"
 
 
+def _operator_opts(operator_response: dict, p) -> dict:
+    """ops / n_matsubara / omega / eta of a run's `operator_response` option:
+    the vertices built once (vertices.build), the χ'' grid as (start, step,
+    count) or None, eta defaulting to the run's."""
+    extra = set(operator_response) - {"ops", "n_matsubara", "omega", "eta"}
+    if extra:
+        raise ValueError(f"operator_response: unknown keys {sorted(extra)}")
+    names = [(str(kind), (int(m[0]), int(m[1]))) for kind, m in operator_response.get("ops", [("density", (0, 0))])]
+    if not names:
+        raise ValueError("operator_response: ops is empty")
+    verts = [VX.build(kind, p, mx, my) for kind, (mx, my) in names]
+    omega = operator_response.get("omega")
+    if omega is not None:
+        bad = set(omega) - {"start", "step", "count"}
+        if bad or set(omega) != {"start", "step", "count"}:
+            raise ValueError("operator_response: omega needs exactly start, step and count")
+        omega = (float(omega["start"]), float(omega["step"]), int(omega["count"]))
+    nl = int(operator_response.get("n_matsubara", 1))
+    if nl < 0 or (nl == 0 and omega is None):
+        raise ValueError("operator_response: n_matsubara >= 0, and an omega grid when it is 0")
+    return dict(names=names, ops=verts, spin_sign=[v.spin_sign for v in verts], n_matsubara=nl, omega=omega,
+                eta=float(operator_response.get("eta", p.eta)))
+
+
+def operator_csv_header(opts: dict) -> str:
+    """sweep, then χ operator by operator, l fastest, named by kind, momentum and l."""
+    return ",".join(["sweep"] + [f"chi_{kind}(mx={mx};my={my};l={l})" for kind, (mx, my) in opts["names"]
+                                 for l in range(opts["n_matsubara"])])
+
+
+def operator_csv_line(sweep: int, chi) -> str:
+    return ",".join(["%d" % sweep] + ["%.12e" % v for v in np.asarray(chi).ravel()]) + "\n"
+
+
+def write_chi2_header(spec_dir: str, opts: dict) -> None:
+    """chi2_omega.npy: the χ'' grid of the operator_response option."""
+    if opts["omega"] is None:
+        return
+    os.makedirs(spec_dir, exist_ok=True)
+    w0, dw, nw = opts["omega"]
+    np.save(os.path.join(spec_dir, "chi2_omega.npy"), w0 + dw * np.arange(nw))
+
+
 class SpectraBins:
     """Bin accumulator of src/Simulation.jl:180-220: sums the spectra of
     bin_size measurements, then writes their mean as group sweep_<i>.  With
     spectral maps (add's `maps`: the ldos / akw of that measurement, each
-    (count, Ly, Lx)) the group also holds their bin means, summed the same way."""
+    (count, Ly, Lx)) the group also holds their bin means, summed the same way;
+    so it does for chi2 ((nops, n_w)) of the operator_response option."""
 
     def __init__(self):
         self.count = 0
@@ -142,8 +187,8 @@ class SpectraBins:
         arrs = [spec.optical_conductivity, spec.dos, spec.dos_AN, spec.A_k_omega0]
         if self.count == 0:
             self.acc = [np.array(a, dtype=np.float64, copy=True) for a in arrs]
-            self.maps = None if maps is None else {k: np.array(maps[k], dtype=np.float64, copy=True)
-                                                   for k in ("ldos", "akw")}
+            self.maps = None if maps is None else {k: np.array(v, dtype=np.float64, copy=True)
+                                                   for k, v in maps.items()}
         else:
             for a, b in zip(self.acc, arrs):
                 a += b
@@ -181,6 +226,7 @@ class ChainOutput:
         self.bins = SpectraBins()
         self.out_dir = out_dir
         self.f_resp = None           # current_response.csv, only with the current_response option
+        self.f_oper = None           # operator_response.csv, only with the operator_response option
 
     def tee(self, msg: str):
         line = f"[{datetime.now().strftime('%Y-%m-%d %H:%M:%S')}] {msg}"
@@ -213,12 +259,24 @@ class ChainOutput:
         self.f_resp.write(response_csv_line(i, dia, lam))
         self.f_resp.flush()
 
+    def operator(self, i, opts, chi):
+        """One row of operator_response.csv (created, with its header, by the first)."""
+        if opts["n_matsubara"] < 1:
+            return
+        if self.f_oper is None:
+            self.f_oper = open(os.path.join(self.out_dir, "operator_response.csv"), "w")
+            self.f_oper.write(operator_csv_header(opts) + "\n")
+        self.f_oper.write(operator_csv_line(i, chi))
+        self.f_oper.flush()
+
     def close(self):
         self.f_log.close()
         self.f_obs.close()
         self.f_trans.close()
         if self.f_resp is not None:
             self.f_resp.close()
+        if self.f_oper is not None:
+            self.f_oper.close()
 
 
 def thermalize(cache, p, state, out: ChainOutput, n_therm: int, Nt_therm_init: int, rng):
@@ -257,14 +315,19 @@ class TransportQueue:
     window (measure_spectral_maps, batched the same way) into the bins.
     current_response (direction / q / n_matsubara, or None): every
     measurement also appends its row (sweep, dia, Λ) to current_response.csv
-    (measure_current_response, batched the same way)."""
+    (measure_current_response, batched the same way).  operator_response
+    (ops / n_matsubara / omega / eta, or None): every measurement also
+    appends its row (sweep, χ) to operator_response.csv and puts χ''(ω) into
+    the bins as chi2 (measure_operator_response, batched the same way)."""
 
     def __init__(self, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int, chain: int = 0,
-                 spectral_maps: dict | None = None, current_response: dict | None = None):
+                 spectral_maps: dict | None = None, current_response: dict | None = None,
+                 operator_response: dict | None = None):
         self.ctx, self.p, self.out, self.res = ctx, p, out, res
         self.bin_size, self.batch, self.chain = bin_size, max(1, int(batch)), chain
         self.window = None if spectral_maps is None else _maps_window(spectral_maps)
         self.response = None if current_response is None else _response_opts(current_response)
+        self.operator = None if operator_response is None else _operator_opts(operator_response, p)
         self.pending = []            # (sweep, Δ snapshot)
 
     def add(self, sweep: int, Delta):
@@ -292,14 +355,33 @@ class TransportQueue:
             resp = self.ctx.measure_current_response(chain=self.chain, deltas=deltas, **self.response)
             if deltas is None:
                 resp = dict(dia=[resp["dia"]], lam=[resp["lam"]])
+        oper = None
+        if self.operator is not None:
+            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
+            oper = measure_operator_option(self.ctx, self.operator, self.chain, deltas)
         for k, ((i, _), r) in enumerate(zip(self.pending, specs)):
             spec = H.SpectrumResult(**r)
-            self.out.transport(i, spec, self.bin_size,
-                               None if maps is None else {"ldos": maps["ldos"][k], "akw": maps["akw"][k]})
+            extra = None if maps is None else {"ldos": maps["ldos"][k], "akw": maps["akw"][k]}
+            if oper is not None and self.operator["omega"] is not None:
+                extra = dict(extra or {}, chi2=oper["chi2"][k])
+            self.out.transport(i, spec, self.bin_size, extra)
             self.res.transport.append((i, spec))
             if resp is not None:
                 self.out.response(i, self.response, float(resp["dia"][k]), resp["lam"][k])
+            if oper is not None:
+                self.out.operator(i, self.operator, oper["chi"][k])
         self.pending = []
+
+
+def measure_operator_option(ctx, opts: dict, chain: int, deltas) -> dict:
+    """measure_operator_response for the operator_response option: chi
+    (nstates, nops, n_matsubara) and chi2 (nstates, nops, n_w), one state at
+    the device Δ when deltas is None."""
+    r = ctx.measure_operator_response(opts["ops"], opts["spin_sign"], n_matsubara=opts["n_matsubara"],
+                                      omega=opts["omega"], eta=opts["eta"], chain=chain, deltas=deltas)
+    if deltas is None:
+        return dict(chi=r["chi"][None], chi2=r["chi2"][None])
+    return r
 
 
 def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_measure: int = 500,
@@ -307,7 +389,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
                    bin_size: int = 5, verbose: bool = True, rng: np.random.Generator | None = None,
                    device: int = 0, delta_cap: float = 0.0, state: H.SimulationState | None = None,
                    cache: H.ComputeCache | None = None, transport_batch: int = 1,
-                   spectral_maps: dict | None = None, current_response: dict | None = None) -> SimulationResult:
+                   spectral_maps: dict | None = None, current_response: dict | None = None,
+                   operator_response: dict | None = None) -> SimulationResult:
     """src/Simulation.jl:34-236.  Files in out_dir: simulation.log (appended),
     observables.csv, transport.csv (one row per transport measurement, every
     measure_transport_freq sweeps; <= 0 disables), and spectra_bins/ — the
@@ -327,10 +410,20 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
     FermionContext.measure_current_response): every transport measurement
     also appends one row (sweep, dia, then Λ(q, iΩ_l) momentum by momentum, l
     fastest) to current_response.csv, whose header names the momenta.  None
-    (the default): no such file, everything else as without the option."""
+    (the default): no such file, everything else as without the option.
+    operator_response = dict(ops=[(kind, (mx, my)), ...], n_matsubara=,
+    omega=dict(start=, step=, count=), eta=) (each optional; kind a key of
+    vertices.KINDS; FermionContext.measure_operator_response): every transport
+    measurement also appends one row (sweep, then χ(iΩ_l) operator by
+    operator, l fastest) to operator_response.csv, whose header names kind,
+    momentum and l, and with an omega grid each sweep_<i>.npz gains the bin
+    mean chi2 ((nops, count)) with the grid in spectra_bins/chi2_omega.npy
+    (eta defaults to the run's).  None (the default): no such files,
+    everything else as without the option."""
     rng = rng if rng is not None else np.random.default_rng()
     if current_response is not None:
         _response_opts(current_response)
+    oper_opts = None if operator_response is None else _operator_opts(operator_response, p)
     out = ChainOutput(out_dir, verbose)
     try:
         out.header(p, n_therm, n_measure, measure_transport_freq, bin_size)
@@ -345,6 +438,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
             write_spectra_header(out.spec_dir, p)
             if spectral_maps is not None:
                 write_maps_header(out.spec_dir, p, spectral_maps)
+            if oper_opts is not None:
+                write_chi2_header(out.spec_dir, oper_opts)
         Nt_fin, acc_th = thermalize(cache, p, state, out, n_therm, Nt_therm_init, rng)
 
         dt_meas = H.calc_optimal_dt(p.beta, p.J, p.mass, Nt_measure)
@@ -354,7 +449,7 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         acc_total = 0
         res = SimulationResult(Nt_fin, acc_th, 0.0)
         tq = TransportQueue(cache.require(), p, out, res, bin_size, transport_batch, spectral_maps=spectral_maps,
-                            current_response=current_response)
+                            current_response=current_response, operator_response=operator_response)
         for i in range(1, n_measure + 1):
             acc, dH = H.hmc_sweep(cache, p, state, Nt=Nt_measure, dt=dt_meas, rng=rng)
             acc_total += int(acc)
@@ -377,7 +472,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                           Nt_therm_init: int = 10, Nt_measure: int = 5, measure_transport_freq: int = 1,
                           bin_size: int = 5, verbose: bool = False, device: int = 0,
                           delta_cap: float = 0.0, transport_batch: int = 1,
-                          spectral_maps: dict | None = None, current_response: dict | None = None) -> list:
+                          spectral_maps: dict | None = None, current_response: dict | None = None,
+                          operator_response: dict | None = None) -> list:
     """len(out_dirs) independent run_simulation's (src/Simulation.jl:34-236),
     chain k writing out_dirs[k] and drawing from rngs[k] in the reference's
     order (initialize_state, then per sweep randn(ComplexF64) and rand() only
@@ -393,11 +489,12 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
     backend: on the device the batched context selects one pole set for the
     largest spectral bound over the chains, and a guard trip re-selects it
     for every chain, so dH differs at ~1e-12 and a Metropolis decision can
-    differ).  spectral_maps, current_response: as run_simulation's, for every
-    chain."""
+    differ).  spectral_maps, current_response, operator_response: as
+    run_simulation's, for every chain."""
     K = len(out_dirs)
     window = None if spectral_maps is None else _maps_window(spectral_maps)
     response = None if current_response is None else _response_opts(current_response)
+    oper_opts = None if operator_response is None else _operator_opts(operator_response, p)
     if len(rngs) != K or K < 1:
         raise ValueError("one rng per output directory")
     outs = [ChainOutput(d, verbose) for d in out_dirs]
@@ -414,6 +511,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                 write_spectra_header(outs[k].spec_dir, p)
                 if spectral_maps is not None:
                     write_maps_header(outs[k].spec_dir, p, spectral_maps)
+                if oper_opts is not None:
+                    write_chi2_header(outs[k].spec_dir, oper_opts)
             Nt_fin, acc_th = thermalize(cache, p, st, outs[k], n_therm, Nt_therm_init, rngs[k])
             cache.ctx.close()
             states.append(st)
@@ -432,7 +531,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
             t1 = time.time()
             acc_total = np.zeros(K, dtype=np.int64)
             tqs = [TransportQueue(ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k,
-                                  spectral_maps=spectral_maps, current_response=current_response)
+                                  spectral_maps=spectral_maps, current_response=current_response,
+                                  operator_response=operator_response)
                    for k in range(K)] if transport_batch > 1 else None
             for i in range(1, n_measure + 1):
                 noise = np.stack([H.standard_complex_normal(r, (p.N, 2)) for r in rngs])
@@ -459,11 +559,16 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                         if window is not None:
                             m = ctx.measure_spectral_maps(p.eta, p.domega, p.omega_max, chain=k, **window)
                             maps = {"ldos": m["ldos"][0], "akw": m["akw"][0]}
+                        oper = None if oper_opts is None else measure_operator_option(ctx, oper_opts, k, None)
+                        if oper is not None and oper_opts["omega"] is not None:
+                            maps = dict(maps or {}, chi2=oper["chi2"][0])
                         outs[k].transport(i, spec, bin_size, maps)
                         results[k].transport.append((i, spec))
                         if response is not None:
                             r = ctx.measure_current_response(chain=k, **response)
                             outs[k].response(i, response, r["dia"], r["lam"])
+                        if oper is not None:
+                            outs[k].operator(i, oper_opts, oper["chi"][0])
                     if i % 10 == 0:
                         outs[k].tee("Meas %d/%d. Acc=%.2f. E=%.4f" % (i, n_measure, acc_total[k] / i,
                                                                      obs.total_energy))

@@ -182,7 +182,7 @@ int dwh_stream(dwh_ctx* ctx, void** stream);
  * (bit 0 "gj_update", bit 1 "gj_pivot", bit 2 "assemble", bit 3 "contract",
  * bit 4 "step", bit 5 "gj_edge", bit 6 "cr_gemm", bit 7 "cr_inv", bit 8 "cr_inv_side",
  * bit 9 "eig_own", bit 10 "eig_vendor", bit 11 "cr_sparse", bit 12 "spectral",
- * bit 13 "response");
+ * bit 13 "response", bit 14 "operator");
  * 0 disables, -1 times everything. */
 int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
 /* name: "gj_update" (rank-128 paired / rank-64 trailing updates),
@@ -197,7 +197,9 @@ int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
  * Lorentzian tables and the two products; work = 2·N·2N·count flops per map
  * per state), "response" (everything dwh_measure_current_response does after
  * its eigensolve, one record per state; work = 8·(2N)³ flops per momentum per
- * state, the J_nm product's), "assemble",
+ * state, the J_nm product's), "operator" (the same for
+ * dwh_measure_operator_response; work = 8·(2N)³ flops per operator per
+ * state), "assemble",
  * "contract", "step"; returns total milliseconds, launches and the
  * algorithmic work summed over launches (fp64 flops; HBM bytes for
  * "assemble"). */
@@ -366,6 +368,61 @@ int dwh_measure_current_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, c
  * "response" timer's per-momentum time is compared against.  Overwrites the
  * slot's JU.  DWH_ERR_STATE before the context's first measurement. */
 int dwh_bench_response_product(dwh_ctx* ctx, int64_t reps, double* ms);
+
+/* ---- response of any one-body operator ------------------------------------
+ * The Kubo bubble of the current response with the vertex supplied by the
+ * caller: charge and spin susceptibilities, Raman vertices, the current at
+ * any q and direction (vertices.py builds these).  In the Nambu basis
+ * ψ = (c_{i↑}; d_i = c†_{i↓}) with E_n, U the eigenpairs of H_BdG(Δ) and
+ * f_n = logistic(-β E_n), an operator
+ *   O = Σ_ij V_ij (c†_{i↑} c_{j↑} + s c†_{i↓} c_{j↓})
+ * with V any complex N x N sparse matrix and s = +1 (spin-even: charge,
+ * current, Raman) or -1 (spin-odd: S^z) has the Nambu matrix
+ *   Ṽ = V ⊕ (-s V^T)
+ * (plain transpose: c†_{i↓} c_{j↓} = δ_ij - d_j† d_i; the constant s Tr V
+ * drops out of the response).  For the antisymmetric Jq and s = +1 this is
+ * Jq ⊕ Jq.  With V_nm = (U^H Ṽ U)[n, m]:
+ *   χ(l)   = (1/N) Σ_{n,m<2N} r_nm(l) |V_nm|²,  r_nm(l) exactly as in
+ *            dwh_measure_current_response (so Re χ for a non-Hermitian V)
+ *   χ''(ω) = (π/N) Σ_{n,m<2N} (f_n - f_m) |V_nm|² L_η(ω - (E_m - E_n)),
+ *            L_η(x) = (1/π) η/(x² + η²), over all ordered pairs, those with
+ *            |f_n - f_m| < 1e-12 skipped: the σ(ω) loop of
+ *            [src/Observables.jl:415-423] without its 1/ω; ω = w_start +
+ *            j·w_step, j < n_w, of either sign or zero.
+ * Operators: nops matrices on one CSR pattern (N rows, 0-based, rowptr N + 1
+ * entries, col nnz entries; the union of several patterns with explicit zeros
+ * is fine), operator k's nnz values at val + k·nnz, spin_sign[k] = ±1.
+ * Duplicate (row, col) entries are summed; columns inside a row may be
+ * unsorted.  Delta / nstates / chain as in dwh_measure_current_response; the
+ * context's own Δ is not touched; works on contexts of every algorithm; one
+ * eigensolve per state.  Outputs:
+ *   chi[l + n_matsubara·(k + nops·s)],  chi2[j + n_w·(k + nops·s)].
+ * n_matsubara = 0 skips the Matsubara part, n_w = 0 the real-frequency part
+ * (the matching pointer may then be NULL; both 0 is DWH_ERR_ARG).  Per
+ * operator and state one 2N-cubed product on the library's own MFMA kernel
+ * between Ṽ U (a sparse kernel) and the pair sums (dwhmc_operator.hip,
+ * dwhmc_response.hip), every sum in a fixed order: two calls give the same
+ * bits, a batch of snapshots equals its single-state calls and a call split
+ * into smaller groups equals the unsplit one.  Operators run in the groups of
+ * the current response (two 2N x 2N work matrices per operator within 2 GiB,
+ * at most 64 per group, DWHMC_RESPONSE_GROUP=g lowers it); χ'' adds
+ * min(2N, 512)·n_w doubles of partial sums per operator of a group.
+ * DWH_ERR_ARG, nothing launched: NULL context, nops < 1, nnz < 1, rowptr not
+ * starting at 0 / not ending at nnz / decreasing, a column outside [0, N), a
+ * sign other than ±1, a negative count, a missing pointer, eta <= 0 with
+ * n_w > 0, non-finite eta / w_start / w_step. */
+int dwh_measure_operator_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta,
+                                  int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
+                                  const dwh_c128* val, const int32_t* spin_sign,
+                                  int64_t n_matsubara, double* chi,
+                                  double eta, double w_start, double w_step, int64_t n_w, double* chi2);
+/* Host only (no device, no context): the validation of the call above and the
+ * 2N-row CSR it uploads — rows < N hold V, row N + j holds -s V[i, j] at
+ * column N + i, duplicates summed — expanded to dense: out holds nops
+ * matrices Ṽ_k, 2N x 2N column-major.  Errors as above, the text where
+ * dwh_last_error(NULL) reads it. */
+int dwh_debug_operator_nambu(int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
+                             const dwh_c128* val, const int32_t* spin_sign, dwh_c128* out);
 
 /* ---- assembly read-back (parity tests; not on the hot path) -------------
  * The BdG matrix H_BdG(Δ) exactly as the device assembles it, so tests can

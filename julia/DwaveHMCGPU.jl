@@ -239,6 +239,35 @@ function measure_current_response(cache::GPUCache, p::ModelParameters; direction
     return dia[], Λ
 end
 
+# The response of any one-body operators O_k = Σ_ij V_ij (c†_{i↑} c_{j↑} + s_k
+# c†_{i↓} c_{j↓}) for the Δ the context holds (dwh_measure_operator_response;
+# Nambu matrix V ⊕ (-s Vᵀ)), the generic CSR form: one pattern for all
+# operators, 0-based (`rowptr` of N + 1 entries, `col` of nnz entries,
+# duplicates add up), `val[e, k]` the nnz values of operator k, `spin_sign[k]`
+# = ±1.  Returns (χ, χ2): χ[l + 1, k] at Ω_l = 2π l/β, l < n_matsubara, in the
+# conventions of measure_current_response's Λ, and χ2[j + 1, k] = χ''(ω_j) on
+# ω_j = ω_start + j·ω_step, j < n_ω (σ(ω)'s conventions without its 1/ω; ω of
+# either sign; needs η > 0).  n_matsubara = 0 or n_ω = 0 skips that part.
+function measure_operator_response(cache::GPUCache, p::ModelParameters, rowptr::Vector{Int64},
+                                   col::Vector{Int64}, val::Matrix{ComplexF64}, spin_sign::Vector{Int32};
+                                   n_matsubara::Integer=1, η::Real=p.η, ω_start::Real=0.0, ω_step::Real=0.0,
+                                   n_ω::Integer=0)
+    nnz, nops = size(val)
+    length(col) == nnz || throw(ArgumentError("val must be nnz x nops with nnz = length(col)"))
+    length(rowptr) == p.N + 1 || throw(ArgumentError("rowptr must have N + 1 entries"))
+    length(spin_sign) == nops || throw(ArgumentError("one spin sign per operator"))
+    χ = zeros(max(n_matsubara, 0), nops)
+    χ2 = zeros(max(n_ω, 0), nops)
+    GC.@preserve rowptr col val spin_sign χ χ2 check(cache.ctx, ccall((:dwh_measure_operator_response, libdwhmc), Cint,
+                           (Ptr{Cvoid}, Int64, Int64, Ptr{ComplexF64}, Int64, Ptr{Int64}, Ptr{Int64}, Int64,
+                            Ptr{ComplexF64}, Ptr{Int32}, Int64, Ptr{Float64}, Float64, Float64, Float64, Int64,
+                            Ptr{Float64}),
+                           cache.ctx, 0, 1, C_NULL, nops, pointer(rowptr), pointer(col), nnz, pointer(val),
+                           pointer(spin_sign), n_matsubara, n_matsubara > 0 ? pointer(χ) : C_NULL,
+                           Float64(η), Float64(ω_start), Float64(ω_step), n_ω, n_ω > 0 ? pointer(χ2) : C_NULL))
+    return χ, χ2
+end
+
 # ---------------------------------------------------------------------------
 # run_simulation on the GPU.  The reference constructs its cache inside the
 # driver (`cache = initialize_cache(p)`, src/Simulation.jl:82), so the driver
