@@ -975,8 +975,19 @@ __global__ __launch_bounds__(64) void k_eig_invit(const double* __restrict__ d, 
   }
   const double tn = tnorm[k];
   const double small = tn > 0.0 ? DBL_EPSILON * tn : DBL_EPSILON;
-  invit_one(lds, lds + n, n, E[(int64_t)k * n + j], j, small, Zt + k * sZ, U0 + k * sZ, U1 + k * sZ,
-            U2 + k * sZ);
+  // Inside a cluster (gaps within kEigClusterTol ||T||) the shifts are kept
+  // kEigClusterSep ||T|| apart (eig_cluster_shift).  The bisected values of an
+  // exactly degenerate level differ by ulps; solved at them, every member
+  // weights the eigenspace's directions by the same 1 / (E_i - lam)^2, ratios
+  // of up to 1e3 per solve, so the cluster's vectors turn nearly parallel
+  // (clean 6 x 6, Delta = 0 in the prototype: cond(Z^T Z) 6e8 after two solves,
+  // 5e13 after three; a 44-fold level at 12 x 12: 5e12 after two) and
+  // k_eig_orth's / long_clusters' Cholesky QR amplifies their rounding by
+  // sqrt(cond).  Apart, the members see the eigenspace differently: cond
+  // 1e4 .. 1e7, residual 1e-15 ||T||.  Levels of a run that bisection
+  // resolves keep their own values and vectors.
+  invit_one(lds, lds + n, n, eig_cluster_shift(E + (int64_t)k * n, j, 0, tn), j, small, Zt + k * sZ,
+            U0 + k * sZ, U1 + k * sZ, U2 + k * sZ);
 }
 
 // Clusters (runs of eigenvalues with consecutive gaps <= ctol ||T||, up to

@@ -406,6 +406,25 @@ constexpr int kEigMaxN = 5120;              // rows k_eig_step holds in register
 // round 3 made runs of >64 "clustered" levels from n ~ 3000 on; runs that
 // long are now orthonormalised by the host-driven Cholesky QR.)
 constexpr double kEigClusterTol = 1e-6;
+// Inside such a run the inverse-iteration shifts are kept at least this x
+// ||T|| apart (eig_cluster_shift; xSTEIN's perturbation of close eigenvalues):
+// above the ulp spread of an exactly degenerate level's bisected values, so
+// that its members do not all weight the eigenspace alike and come out nearly
+// parallel; levels that bisection resolves by more keep their own values.
+constexpr double kEigClusterSep = 8 * 2.220446049250313e-16;
+// The shift of level j of the ascending E[0, n) (jlo: the first index whose
+// vector is computed): sigma_j = max(E_j, sigma_{j-1} + sep) along the run that
+// j belongs to, in closed form max_i (E_i + (j - i) sep) over the run's levels
+// i <= j.  E_j itself outside runs (one comparison).
+__host__ __device__ inline double eig_cluster_shift(const double* E, int j, int jlo, double tn) {
+  const double ctol = kEigClusterTol * tn, sep = kEigClusterSep * tn;
+  double lam = E[j];
+  for (int i = j; i > jlo && E[i] - E[i - 1] <= ctol; --i) {
+    const double c = E[i - 1] + (j - i + 1) * sep;
+    lam = c > lam ? c : lam;
+  }
+  return lam;
+}
 // the particle-hole half solve computes the partners' vectors itself unless
 // the gap below c0 exceeds this (the partner images are not orthogonalised
 // against the computed vectors: their overlap is ~eps ||T|| / gap)

@@ -521,6 +521,7 @@ int dwh::eigen_solve(dwh_ctx* ctx, const TrSrc& src, int m) {
   const bool own = n2 <= dwh::kEigMaxN;
   ctx->eig_ph = false;
   ctx->eig_ph_last = 0;   // dwh_info_t::eig_half describes this solve on every exit path
+  ctx->eig_quat_last = 0;   // and eig_quat: 0 on the rocSOLVER route and after a zheev re-solve
   HIPCHECK(ctx, hipMemsetAsync(ctx->d_tr_bad, 0, sizeof(int), ctx->stream));
   if (own) {
     // the own solver (k_eig_orth flags an over-long cluster in d_tr_bad);
@@ -549,6 +550,7 @@ int dwh::eigen_solve(dwh_ctx* ctx, const TrSrc& src, int m) {
   ctx->eig_ph_last = ctx->eig_ph ? 1 : 0;
   if (bad) {
     Scope sc(ctx, T_EIG_VENDOR, m);
+    ctx->eig_quat_last = 0;   // the result is rocSOLVER's
     rc = eigen_enqueue(ctx, src, m, true);
   }
   return rc;

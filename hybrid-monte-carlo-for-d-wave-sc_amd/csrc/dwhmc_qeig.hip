@@ -62,7 +62,6 @@ constexpr int kQTB = 64;     // pass tile: rows x columns
 #endif
 constexpr double kQInvitShare = QINVIT_SHARE;   // bound on the other eigenvectors' share after one solve
 constexpr int kQMaxCluster = 32;   // longest eigenvalue cluster the structure-preserving solver orthonormalises
-constexpr double kQClusterShift = 1e-12;   // a cluster member's inverse-iteration shift below its level, x ||T||
 constexpr int kQRS = 1024;   // k_q_rs threads
 constexpr int kQMaxR = 3;    // rows per k_q_rs thread: M <= kQMaxM
 }  // namespace
@@ -948,19 +947,19 @@ __global__ __launch_bounds__(64) void k_q_invit(const double* __restrict__ ra, c
   const int jj = blockIdx.x * blockDim.x + threadIdx.x;
   if (jj >= nv) return;
   const double tn = tnorm[k];
-  // A member of a cluster (a neighbour within kEigClusterTol ||T||) is solved
-  // at e - kQClusterShift ||T||: for an exactly degenerate level the members'
-  // bisected values differ by ulps, and solving at them weights the
-  // eigenspace's directions by 1 / (E_i - e) — ratios of 10..1000, so the
-  // vectors turn nearly parallel and k_q_orth's Cholesky QR amplifies their
-  // out-of-cluster rounding by as much (clean 10 x 10: residual 3e-13,
-  // 1.5e-12 against the Theta partners).  A shift far above the ulp spread
-  // and far below the gap to the next level weights the eigenspace evenly.
+  // Inside a cluster (gaps within kEigClusterTol ||T||) the shifts are kept
+  // kEigClusterSep ||T|| apart (eig_cluster_shift): for an exactly degenerate
+  // level the members' bisected values differ by ulps, and solving at them
+  // weights the eigenspace's directions by 1 / (E_i - e) — ratios of 10..1000,
+  // the same for every member, so the vectors turn nearly parallel and
+  // k_q_orth's Cholesky QR amplifies their rounding by as much (clean 10 x
+  // 10: residual 3e-13, 1.5e-12 against the Theta partners).  (One shift of
+  // 1e-12 ||T|| below every member, as here before, cures that but mixes
+  // the levels of a run that bisection resolves at gaps near it: 5e-13 at
+  // 6 x 6 with 1e-9 of disorder in the prototype, against 6e-16.)
   const double* Ek = E + (int64_t)k * n;
   const double e = Ek[j0 + jj];
-  const double ctol = kEigClusterTol * tn;
-  const bool member = (jj > 0 && e - Ek[j0 + jj - 1] <= ctol) || (j0 + jj + 1 < n && Ek[j0 + jj + 1] - e <= ctol);
-  const double lam = member ? e - kQClusterShift * tn : e;
+  const double lam = eig_cluster_shift(Ek, j0 + jj, j0, tn);
   const double small = tn > 0.0 ? DBL_EPSILON * tn : DBL_EPSILON;
   double2* z = Zt + k * sZ + jj;
   double2* sc = S + k * sS + jj;
@@ -1195,9 +1194,7 @@ __global__ __launch_bounds__(64) void k_q_invit16(const double* __restrict__ ra,
   const double tn = tnorm[k];
   const double* Ek = E + (int64_t)k * n;
   const double e = Ek[j0 + jj];
-  const double ctol = kEigClusterTol * tn;
-  const bool member = (jj > 0 && e - Ek[j0 + jj - 1] <= ctol) || (j0 + jj + 1 < n && Ek[j0 + jj + 1] - e <= ctol);
-  const double lam = member ? e - kQClusterShift * tn : e;   // (k_q_invit)
+  const double lam = eig_cluster_shift(Ek, j0 + jj, j0, tn);   // (k_q_invit)
   const double small = tn > 0.0 ? DBL_EPSILON * tn : DBL_EPSILON;
   double2* z = Zt + k * sZ + jj;
   double2* sc = S + k * sS + jj;

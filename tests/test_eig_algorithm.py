@@ -217,6 +217,103 @@ def test_quaternion_reduction_bdg_lattices(oracle, Lx, Ly, clean, mu):
     assert np.max(np.abs(U.conj().T @ U - np.eye(2 * N))) <= 1e-12
 
 
+# --------------------------------------------------------------------------
+# Spectra at the solvers' own thresholds (tests/eig_cases.py): exact clusters,
+# degeneracies lifted through kEigClusterTol, central gaps around kEigZeroTol,
+# reducible and tiny matrices.  The same tolerances as above (_check).
+import eig_cases as EC  # noqa: E402
+
+
+def _cpu_names(family):
+    return [n for n in EC.names(family) if "16x16" not in n]   # n <= 288 here; the device test runs n = 512
+
+
+def _run_member(oracle, family, name):
+    c = EC.member(oracle, family, name)
+    for solve in (P.eigh_bdg, P.eigh):
+        lam, U = solve(c.H)
+        _check(c.H, lam, U)
+    if c.p.N <= 40:
+        lam, U = QP.eigh_quat(c.H)
+        _check(c.H, lam, U)
+
+
+@pytest.mark.parametrize("name", _cpu_names("clean"))
+def test_family_clean_ladder(oracle, name):
+    """Exactly degenerate shells (runs of 4 .. 16 levels, 12 / 28 / 44 at zero
+    for the nested Fermi surface).  clean-6x6-mu-1-d0 (runs of 12) had a
+    residual of 3.4e-11 (1 + max|E|) before cluster members were solved at a
+    shifted level (CLUSTER_SHIFT): cond(Z^T Z) = 5e13 before Cholesky QR."""
+    _run_member(oracle, "clean", name)
+
+
+@pytest.mark.parametrize("name", _cpu_names("lifted"))
+def test_family_lifted_degeneracies(oracle, name):
+    _run_member(oracle, "lifted", name)
+
+
+@pytest.mark.parametrize("name", _cpu_names("zero"))
+def test_family_zero_gap_ladder(oracle, name):
+    _run_member(oracle, "zero", name)
+
+
+@pytest.mark.parametrize("name", _cpu_names("reducible"))
+def test_family_reducible_and_tiny(oracle, name):
+    _run_member(oracle, "reducible", name)
+
+
+def test_family_conditions(oracle):
+    """The families reach what they are for: a ladder that stops exercising a
+    threshold fails here."""
+    clean = EC.clean_ladder(oracle)
+    assert max(c.cls["longest_run_away"] for c in clean) >= 16
+    assert any(12 <= c.cls["longest_run_away"] < 16 for c in clean)
+    assert max(c.cls["zero_run"] for c in clean) > 16
+    assert any(EC.predict_quat(c.cls) == 0 for c in clean)       # a crowd the structure-preserving solver declines
+    by = {c.name: c for c in clean}
+    assert by["clean-6x6-mu-1-d0"].cls["longest_run"] == 12
+    assert by["clean-12x12-mu-1-d0"].cls["longest_run"] == 16
+    assert by["nested-8x8"].cls["zero_run"] == 28
+    lifted = EC.lifted_ladder(oracle)
+    assert any(c.cls["longest_run"] >= 8 for c in lifted) and any(c.cls["longest_run_hi"] == 1 for c in lifted)
+    assert max(c.cls["mid_gaps"] for c in lifted) >= 40
+    zero = EC.zero_gap_ladder(oracle)
+    for c in zero:
+        target = float(c.name.rsplit("-g", 1)[1]) * EC.ZERO_TOL
+        assert abs(c.cls["g0"] - target) <= 0.1 * target, (c.name, c.cls["g0"])
+        assert c.cls["longest_run_hi"] == 1, c.name
+    assert {EC.predict_half_one_stage(c.cls) for c in zero} >= {0, 1}
+    red = EC.reducible(oracle)
+    assert all(c.cls["longest_run_hi"] == 1 for c in red)
+    assert {2, 4} <= {c.cls["n"] for c in red}
+    for fam in EC.FAMILIES:
+        assert [c.name for c in EC.FAMILIES[fam](oracle)] == EC.names(fam)
+        assert all(c.cls["n"] <= 512 for c in EC.FAMILIES[fam](oracle))
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 9, 24])
+def test_columnwise_solves_match_scalar(n):
+    """lu_tridiag_many / lu_solve_many / sturm_count_many (every shift at once)
+    are lu_tridiag / lu_solve / sturm_count per column, bit for bit."""
+    rng = np.random.default_rng(n)
+    d, e = rng.standard_normal(n), rng.standard_normal(max(n - 1, 0))
+    if n > 4:
+        e[2] = 0.0
+        d[3] = d[4] = 0.25          # a zero pivot without interchange
+    lam = np.concatenate([np.linalg.eigvalsh(np.diag(d) + np.diag(e, 1) + np.diag(e, -1)), [0.25, 0.1]])
+    small = 1e-16
+    Y = rng.standard_normal((n, len(lam)))
+    fac = P.lu_tridiag_many(d, e, lam, small)
+    X = P.lu_solve_many(*fac, Y)
+    for m, l in enumerate(lam):
+        f1 = P.lu_tridiag(d, e, l, small)
+        for a, b in zip(fac, f1):
+            assert np.array_equal(a[:, m], b)
+        assert np.array_equal(X[:, m], P.lu_solve(*f1, Y[:, m]))
+    cnt = P.sturm_count_many(d, e * e, lam, 1e-300)
+    assert [int(c) for c in cnt] == [P.sturm_count(d, e * e, l, 1e-300) for l in lam]
+
+
 def _qmul(a1, b1, a2, b2):
     """quat(a1, b1) quat(a2, b2), quat(al, be) = [[al, -conj be], [be, conj al]] (k_q_rot's qmul)."""
     return a1 * a2 - np.conj(b1) * b2, b1 * a2 + np.conj(a1) * b2

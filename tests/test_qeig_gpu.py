@@ -33,7 +33,8 @@ def _ctx(m, O, L, clean, seed):
 
 @pytest.mark.parametrize("L", [4, 6, 8, 12, 16])
 @pytest.mark.parametrize("clean", [False, True])
-def test_eigenvalues_only_matches_lapack(dwhmc, oracle, L, clean):
+def test_eigenvalues_only_matches_lapack(dwhmc, oracle, monkeypatch, L, clean):
+    monkeypatch.delenv("DWHMC_EIG_QUAT", raising=False)
     ctx, H = _ctx(dwhmc, oracle, L, clean, 100 + L)
     try:
         ev = np.linalg.eigvalsh(H)
@@ -43,8 +44,12 @@ def test_eigenvalues_only_matches_lapack(dwhmc, oracle, L, clean):
         # backward-stable reduction + bisection to the last bit: a few eps ||H|| (n up to 512)
         assert np.max(np.abs(E - ev)) / scale < 2e-13
         assert np.all(np.diff(E) >= 0)
-        # the same spectrum as the full (one-stage) eigensystem
+        # the same spectrum as the full eigensystem of the one-stage solver
+        # (DWHMC_EIG_QUAT=0: by default the full solve takes the same reduction)
+        monkeypatch.setenv("DWHMC_EIG_QUAT", "0")
         E1, _ = ctx.eigensystem(0, vectors=True)
+        assert ctx.info["eig_quat"] == 0
+        monkeypatch.delenv("DWHMC_EIG_QUAT")
         assert np.max(np.abs(E - E1)) / scale < 2e-13
         # bit-reproducible (fixed-point integer accumulation of H v)
         E2, _ = ctx.eigensystem(0, vectors=False)

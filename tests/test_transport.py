@@ -217,7 +217,8 @@ def test_own_eigensolver_L48(dwhmc, oracle):
 def test_eigensystem_above_own_limit_vendor_route(dwhmc, oracle):
     """The one size where rocSOLVER is the only route:
     n = 2N = 5200 > kEigMaxN = 5120 (52 x 50) runs zheevd, counted by the
-    eig_vendor timer, and dwh_info_t::eig_half reports 0 for it (ADVICE r05).
+    eig_vendor timer, and dwh_info_t::eig_half and eig_quat report 0 for it
+    (ADVICE r05, r06).
     Size-independent checks, no LAPACK solve of n = 5200 on the host: the
     eigenvalues ascend, Σ E = tr H = 0 and Σ E² = ‖H‖_F² (1e-10 relative),
     and for 96 eigenpairs spread over the spectrum ‖H u − E u‖ ≤ 1e-10
@@ -234,9 +235,9 @@ def test_eigensystem_above_own_limit_vendor_route(dwhmc, oracle):
     ctx.timing_enable(["eig_own", "eig_vendor"])
     E, U = ctx.eigensystem(0)
     own, vendor = ctx.timing_read("eig_own")[1], ctx.timing_read("eig_vendor")[1]
-    half = ctx.info["eig_half"]
+    half, quat = ctx.info["eig_half"], ctx.info["eig_quat"]
     ctx.close()
-    assert (own, vendor) == (0, 1) and half == 0
+    assert (own, vendor) == (0, 1) and half == 0 and quat == 0
     assert np.all(np.isfinite(E)) and np.all(np.isfinite(U))
     assert np.all(np.diff(E) >= 0)
     fro2 = float(np.sum(np.abs(H) ** 2))

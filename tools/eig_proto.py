@@ -8,8 +8,10 @@ seconds, checked against numpy.linalg.eigh.  Not imported by the package.
                       trailing triangle per column)
   eigenvalues         bisection on Sturm counts, one eigenvalue per thread
   eigenvectors        inverse iteration (T - λI = LU with partial pivoting,
-                      three solves), Cholesky QR inside clusters, one
-                      symmetric orthogonalisation step over all vectors
+                      two solves; shifts inside a cluster kept 8 eps ||T||
+                      apart),
+                      Cholesky QR inside clusters, one symmetric
+                      orthogonalisation step over all vectors
   back-transform      U = H_0 H_1 ... H_{n-2} Z, reflectors in blocks of nb
                       as I - V T V^H (forward compact WY), last block first
 """
@@ -142,7 +144,23 @@ def sturm_count(d, e2, lam, pivmin):
     return c
 
 
+def sturm_count_many(d, e2, lam, pivmin):
+    """sturm_count for an array of shifts at once (the same recurrence per entry)."""
+    q = d[0] - lam
+    q = np.where(np.abs(q) < pivmin, -pivmin, q)
+    c = (q < 0).astype(np.int64)
+    for k in range(1, len(d)):
+        q = d[k] - lam - e2[k - 1] / q
+        q = np.where(np.abs(q) < pivmin, -pivmin, q)
+        c += q < 0
+    return c
+
+
 def bisect_all(d, e):
+    """Every eigenvalue by bisection from the Gershgorin interval (one
+    eigenvalue per thread on the device; here all of them step together, each
+    stopping when its interval no longer splits), and ||T|| (the Gershgorin
+    bound)."""
     n = len(d)
     e2 = e * e
     r = np.zeros(n)
@@ -153,19 +171,18 @@ def bisect_all(d, e):
     gl -= 2 * np.finfo(float).eps * tnorm * n + 1e-300
     gu += 2 * np.finfo(float).eps * tnorm * n + 1e-300
     pivmin = np.finfo(float).tiny * max(1.0, float(np.max(e2)) if n > 1 else 1.0)
-    lam = np.zeros(n)
-    for j in range(n):
-        lo, hi = gl, gu
-        for _ in range(200):
-            mid = 0.5 * (lo + hi)
-            if mid <= lo or mid >= hi:
-                break
-            if sturm_count(d, e2, mid, pivmin) > j:
-                hi = mid
-            else:
-                lo = mid
-        lam[j] = 0.5 * (lo + hi)
-    return lam, tnorm
+    lo, hi = np.full(n, gl), np.full(n, gu)
+    j = np.arange(n)
+    active = np.ones(n, bool)
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        active &= ~((mid <= lo) | (mid >= hi))
+        if not active.any():
+            break
+        above = sturm_count_many(d, e2, mid, pivmin) > j
+        hi = np.where(active & above, mid, hi)
+        lo = np.where(active & ~above, mid, lo)
+    return 0.5 * (lo + hi), tnorm
 
 
 def lu_tridiag(d, e, lam, small):
@@ -235,34 +252,116 @@ def start_vector(m, n):
     return out
 
 
-def inverse_iteration(d, e, lam, tnorm, cluster_tol=1e-6, iters=3):
-    """Independent inverse iteration per eigenvalue, Cholesky QR (twice) on
-    every cluster (consecutive gaps <= cluster_tol ||T||), then one symmetric
-    orthogonalisation step Z <- Z (3/2 I - 1/2 Z^T Z) over all vectors."""
+def lu_tridiag_many(d, e, lam, small):
+    """lu_tridiag for an array of shifts at once (column m: shift lam[m]); the
+    same operations per column, the branch on the interchange as a select (as
+    the device's lanes, which hold different shifts)."""
+    n, M = len(d), len(lam)
+    u0 = d[:, None] - lam[None, :]
+    u1 = np.repeat(np.concatenate([e, [0.0]])[:, None], M, axis=1)
+    u2 = np.zeros((n, M))
+    lmul = np.zeros((n, M))
+    piv = np.zeros((n, M), bool)
+    sub = np.concatenate([e, [0.0]])
+    for k in range(n - 1):
+        a, b = u0[k].copy(), sub[k]
+        keep = np.abs(a) >= abs(b)
+        a = np.where(keep & (a == 0.0), small, a)
+        m = np.where(keep, b, a) / np.where(keep, a, b)
+        lmul[k] = m
+        piv[k] = ~keep
+        nxt, t = u0[k + 1].copy(), u1[k].copy()
+        u0[k] = np.where(keep, a, b)
+        u1[k] = np.where(keep, t, nxt)
+        u0[k + 1] = np.where(keep, nxt - m * t, t - m * nxt)
+        if k + 1 < n - 1:
+            u2[k] = np.where(keep, 0.0, u1[k + 1])
+            u1[k + 1] = np.where(keep, u1[k + 1], -m * u1[k + 1])
+    u0 = np.where(np.abs(u0) < small, np.where(u0 != 0, np.copysign(small, u0), small), u0)
+    return u0, u1, u2, lmul, piv
+
+
+def lu_solve_many(u0, u1, u2, lmul, piv, Y):
+    """lu_solve, column m of Y with column m of the factors."""
+    n = Y.shape[0]
+    Y = Y.copy()
+    for k in range(n - 1):
+        yk, yk1 = Y[k].copy(), Y[k + 1].copy()
+        Y[k] = np.where(piv[k], yk1, yk)
+        Y[k + 1] = np.where(piv[k], yk - lmul[k] * yk1, yk1 - lmul[k] * yk)
+    X = np.zeros_like(Y)
+    for k in range(n - 1, -1, -1):
+        s = Y[k]
+        if k + 1 < n:
+            s = s - u1[k] * X[k + 1]
+        if k + 2 < n:
+            s = s - u2[k] * X[k + 2]
+        X[k] = s / u0[k]
+    return X
+
+
+# Inside a cluster (consecutive gaps <= cluster_tol ||T||) the inverse-iteration
+# shifts are kept this x ||T|| apart (kEigClusterSep, eig_cluster_shift in
+# csrc/dwhmc_internal.h; xSTEIN's perturbation of close eigenvalues).  The
+# bisected values of an exactly degenerate level differ by ulps: solved at
+# them, every member weights the eigenspace's directions by the same
+# 1 / (E_i - lam)^iters, so the cluster's vectors come out nearly parallel
+# (clean 6 x 6 at Delta = 0: cond(Z^T Z) = 6e8 after two solves, 5e13 after
+# three) and Cholesky QR amplifies each vector's rounding by sqrt(cond) (a
+# residual of 3.4e-11 (1 + max|E|) there with three solves; 7e-13 with two at
+# 12 x 12, tp = mu = Delta = 0).  Apart, the members see the eigenspace
+# differently: cond 1e4 .. 1e7, residual 1e-15.  Levels of a run that bisection
+# resolves by more keep their own values, so a lifted degeneracy keeps its own
+# vectors.  (One shift of 1e-12 ||T|| for every member also cures the exact
+# clusters, but mixes levels 1e-11 ||T|| apart: 4e-11 at 8 x 8 with 1e-9 of
+# disorder.)
+CLUSTER_SEP = 8 * np.finfo(float).eps
+
+
+def cluster_shifts(lam, tnorm, cluster_tol=1e-6, sep=CLUSTER_SEP, j0=0):
+    """sigma_j = max(lam_j, sigma_{j-1} + sep ||T||) along each run of gaps <=
+    cluster_tol ||T|| among the indices >= j0; lam_j outside runs."""
+    s = np.array(lam, dtype=float)
+    for j in range(j0 + 1, len(lam)):
+        if lam[j] - lam[j - 1] <= cluster_tol * tnorm:
+            s[j] = max(lam[j], s[j - 1] + sep * tnorm)
+    return s
+
+
+def inverse_iteration_range(d, e, lam, tnorm, j0, cluster_tol=1e-6, iters=2, sep=CLUSTER_SEP):
+    """Independent inverse iteration for the eigenvalue indices [j0, n)
+    (vectors of T in Z[:, j0:]; two solves from the fixed start, as
+    invit_one) at cluster_shifts; Cholesky QR (twice) on every cluster
+    (consecutive gaps <= cluster_tol ||T||) inside the range, then one
+    symmetric orthogonalisation step Z <- Z (3/2 I - 1/2 Z^T Z) over those
+    columns."""
     n = len(d)
     eps = np.finfo(float).eps
     small = eps * tnorm if tnorm > 0 else eps
-    Z = np.zeros((n, n))
-    for m in range(n):
-        fac = lu_tridiag(d, e, lam[m], small)
-        x = start_vector(m, n)
-        for _ in range(iters):
-            x = lu_solve(*fac, x)
-            x /= np.linalg.norm(x)
-        Z[:, m] = x
-    j = 0
+    shift = cluster_shifts(lam, tnorm, cluster_tol, sep)[j0:]
+    fac = lu_tridiag_many(d, e, shift, small)
+    Z = np.stack([start_vector(m, n) for m in range(j0, n)], axis=1) if n > j0 else np.zeros((n, 0))
+    for _ in range(iters):
+        Z = lu_solve_many(*fac, Z)
+        Z /= np.linalg.norm(Z, axis=0)[None, :]
+    j = j0
     while j < n:
         k = j + 1
         while k < n and lam[k] - lam[k - 1] <= cluster_tol * tnorm:
             k += 1
         if k - j > 1:
             for _ in range(2):
-                C = Z[:, j:k]
+                C = Z[:, j - j0:k - j0]
                 L = np.linalg.cholesky(C.T @ C)
-                Z[:, j:k] = np.linalg.solve(L, C.T).T
+                Z[:, j - j0:k - j0] = np.linalg.solve(L, C.T).T
         j = k
     G = Z.T @ Z
-    return Z @ (1.5 * np.eye(n) - 0.5 * G)
+    return Z @ (1.5 * np.eye(n - j0) - 0.5 * G)
+
+
+def inverse_iteration(d, e, lam, tnorm, cluster_tol=1e-6, iters=2, sep=CLUSTER_SEP):
+    """inverse_iteration_range over every index."""
+    return inverse_iteration_range(d, e, lam, tnorm, 0, cluster_tol, iters, sep)
 
 
 def back_transform(V, tau, Z, nb=8):
@@ -304,36 +403,6 @@ def theta_partner(U, j_src):
     N = U.shape[0] // 2
     u, v = U[:N, j_src], U[N:, j_src]
     return np.concatenate([-np.conj(v), np.conj(u)])
-
-
-def inverse_iteration_range(d, e, lam, tnorm, j0, cluster_tol=1e-6, iters=3):
-    """inverse_iteration for the eigenvalue indices [j0, n) only (vectors of T
-    in Z[:, j0:]); clusters inside the range, then one symmetric
-    orthogonalisation step over those columns."""
-    n = len(d)
-    eps = np.finfo(float).eps
-    small = eps * tnorm if tnorm > 0 else eps
-    Z = np.zeros((n, n - j0))
-    for m in range(j0, n):
-        fac = lu_tridiag(d, e, lam[m], small)
-        x = start_vector(m, n)
-        for _ in range(iters):
-            x = lu_solve(*fac, x)
-            x /= np.linalg.norm(x)
-        Z[:, m - j0] = x
-    j = j0
-    while j < n:
-        k = j + 1
-        while k < n and lam[k] - lam[k - 1] <= cluster_tol * tnorm:
-            k += 1
-        if k - j > 1:
-            for _ in range(2):
-                C = Z[:, j - j0:k - j0]
-                L = np.linalg.cholesky(C.T @ C)
-                Z[:, j - j0:k - j0] = np.linalg.solve(L, C.T).T
-        j = k
-    G = Z.T @ Z
-    return Z @ (1.5 * np.eye(n - j0) - 0.5 * G)
 
 
 def eigh_bdg(A: np.ndarray):

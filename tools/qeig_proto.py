@@ -47,6 +47,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from eig_proto import cluster_shifts
+
 
 def theta(x: np.ndarray) -> np.ndarray:
     """Theta (u; v) = (-conj v; conj u) on the last axis split in halves (or rows)."""
@@ -290,7 +292,8 @@ def inverse_iteration(a, d, b, lam, tnorm, cluster_tol=1e-6, iters=3):
     # blocks then come out as independent combinations)
     small = eps * tnorm * tnorm if tnorm > 0 else eps
     Z = np.zeros((n, len(lam)), complex)
-    for k, l in enumerate(lam):
+    # shifts inside a cluster kept 8 eps ||T|| apart (eig_proto.cluster_shifts; k_q_invit)
+    for k, l in enumerate(cluster_shifts(lam, tnorm, cluster_tol)):
         x = start_vector(k, n)
         for _ in range(iters):
             x = band_solve_pivoted(a, d, b, l, x, eps * tnorm)
