@@ -99,6 +99,7 @@ SIGNATURES = {
     "dwh_debug_operator_nambu": (C.c_int, [_I64, _I64, _P, _P, _I64, _P, _P, _P]),
     "dwh_debug_dense_H": (C.c_int, [_P, _I64, _P]),
     "dwh_debug_qeig": (C.c_int, [_P, _I64, _P, _P]),
+    "dwh_debug_set_eigensystem": (C.c_int, [_P, _I64, _P, _P, _I32]),
     "dwh_debug_level0": (C.c_int, [_P, _I64, _I64, _I32, _P, _P]),
     "dwh_debug_cr_launch": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32,
                                       _P, _I32, _I32, _D]),

@@ -405,6 +405,24 @@ class FermionContext:
         self._c(self._lib.dwh_debug_dense_H(self._h, int(chain), ptr(Hcm)))
         return Hcm.T.copy()
 
+    def debug_set_eigensystem(self, E, U, ph: bool = False):
+        """Stage eigensystems for the next measurement call's eigensolve
+        (dwh_debug_set_eigensystem; one-shot): E (2N,) or (nstates, 2N)
+        ascending, U (2N, 2N) or (nstates, 2N, 2N) with the vector of E[n] in
+        column n.  The next measure_* call with as many states reduces these
+        instead of solving; ph=True also takes transport's particle-hole
+        half sums (column 2N-1-n must be the Nambu partner of column n)."""
+        n2 = 2 * self.N
+        E = np.asarray(E, dtype=np.float64)
+        U = np.asarray(U, dtype=np.complex128)
+        if E.ndim == 1:
+            E, U = E[None], U[None]
+        if E.ndim != 2 or E.shape[1] != n2 or U.shape != (E.shape[0], n2, n2):
+            raise ValueError(f"expected E (nstates, {n2}) and U (nstates, {n2}, {n2})")
+        Ecm = np.ascontiguousarray(E)
+        Ucm = np.ascontiguousarray(np.transpose(U, (0, 2, 1)))     # row c = column c of U
+        self._c(self._lib.dwh_debug_set_eigensystem(self._h, E.shape[0], ptr(Ecm), ptr(Ucm), int(bool(ph))))
+
     def debug_level0(self, chain: int = 0, pole: int = 0, refill: bool = True):
         """(M, y): H_BdG(Δ) - i y_pole I (2N, 2N) from the CR level-0 blocks the
         factorisation consumes (dwh_debug_level0), and the pole heights y_q."""

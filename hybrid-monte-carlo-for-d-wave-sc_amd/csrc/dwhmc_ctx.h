@@ -178,6 +178,13 @@ struct dwh_ctx {
   int64_t eig_long_clusters = 0;   // clusters longer than k_eig_orth's limit, orthonormalised by long_clusters
   int eig_ph_last = -1;    // dwh_info_t::eig_half: eig_ph of the last eigensolve (-1: none yet)
   int eig_quat_last = 0;   // the last eigensolve took the structure-preserving solver
+  // dwh_debug_set_eigensystem: dbg_nstates > 0 eigensystems staged on the
+  // host (E: 2N per state, U: 2N x 2N column-major per state), which the next
+  // eigen_solve with m == dbg_nstates copies into the slots instead of solving
+  int dbg_nstates = 0;
+  bool dbg_ph = false;
+  std::vector<double> dbg_E;
+  std::vector<double2> dbg_U;
   double *d_eig_d = nullptr, *d_eig_e = nullptr, *d_eig_tn = nullptr;
   // structure-preserving solver (dwhmc_qeig.hip) workspace: q_slots matrices
   // (q_bufs), the eigenvector stage's for q_vec_slots (q_heev_enqueue)

@@ -30,6 +30,28 @@ __device__ __forceinline__ double2 cinv(double2 a) {
   const double s = 1.0 / (a.x * a.x + a.y * a.y);
   return make_double2(a.x * s, -a.y * s);
 }
+// Point k of a float range: start + step·k, the product and the sum rounded
+// one after the other, as the host forms the grids it returns
+// (dwh_spectral_window, the bindings' omega arrays).  The pragma matters: HIP's
+// __dmul_rn / __dadd_rn are plain operators, which the device default
+// (-ffp-contract=fast) fuses into one fma — an ulp away on about half the
+// points, and a Lorentzian of width η turns an ulp of ω into ulp/η.
+__device__ __forceinline__ double grid_point(double start, double step, int64_t k) {
+#pragma clang fp contract(off)
+  const double p = step * (double)k;
+  return start + p;
+}
+
+// f_n - f_m of the Fermi factors f = logistic(-βE), g = 1 - f = logistic(+βE)
+// (each from its own exponential), dE = E_m - E_n, without the cancellation of
+// the plain difference: f_n - f_m = f_n g_m (1 - e^{-β dE}) exactly, taken from
+// the side on which the exponential decays.  A few ulp at any gap; the plain
+// difference loses eps / |f_n - f_m| (8e-10 of the l = 0 quotient at
+// dE = 2e-8).
+__device__ __forceinline__ double fermi_diff(double dE, double fn, double gn, double fm, double gm, double beta) {
+  const double x = beta * dE;
+  return x >= 0 ? -(fn * gm) * expm1(-x) : (fm * gn) * expm1(x);
+}
 // 1/a with v_rcp_f64 + two Newton steps (error ~1 ulp; the IEEE division
 // sequence has ~3x the latency and sits on the pivot dependency chain).
 __device__ __forceinline__ double rcp_nr(double d) {

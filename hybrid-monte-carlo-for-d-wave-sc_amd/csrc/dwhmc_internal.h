@@ -292,7 +292,7 @@ void launch_sum_ld(const Dims& d, const double* ldpart, double* ldsum, hipStream
 // measurement (n2 = 2N; U, JU, Jmn: n2 x n2 column-major)
 struct TrBufs {
   double2 *U, *JU, *Jmn;
-  double *E, *f, *dia, *Wn, *wan, *w0, *lam, *dc;   // n2 each
+  double *E, *f, *g, *dia, *Wn, *wan, *w0, *lam, *dc;   // n2 each (g = 1 - f = logistic(+β E))
   double *part, *sigma, *dos, *dos_an, *ak, *scalars;
 };
 // ω grid: w0 + k dw (k < nw); DOS grid: d0 + k dw (k < nd)
@@ -313,7 +313,7 @@ void launch_tr_assemble(double2* A, int N, const int* hcol, const double* hval, 
 // f, the diamagnetic / DOS / antinodal weights and the A(k,0) weight per eigenstate;
 // nbr: 3 x N (+x, +x+y, +x-y neighbours, 0-based)
 void launch_tr_colstats(const double2* U, int N, int Lx, const double* E, double beta, double eta,
-                        double t, double tp, const int* nbr, double* f, double* dia, double* Wn,
+                        double t, double tp, const int* nbr, double* f, double* g, double* dia, double* Wn,
                         double* wan, double* w0, hipStream_t s);
 // JU = (J ⊕ J) U, J in CSR form (N rows, val = Im J)
 // JU[:, :ncol] = (J ⊕ J) U[:, :ncol]
@@ -357,14 +357,14 @@ constexpr int kRsLChunk = 8;
 // f_n = logistic(-β E_n) and the diamagnetic weight per eigenstate for the
 // bond list nbr (3 x N neighbours, 0-based) with hoppings tb[3] (host)
 void launch_rs_colstats(const double2* U, int N, const double* E, double beta, const double* tb, const int* nbr,
-                        double* f, double* dia, hipStream_t s);
+                        double* f, double* g, double* dia, hipStream_t s);
 // JU_q = (Jq ⊕ Jq) U, q < nq: Jq in CSR form (N rows, one pattern, nnz complex
 // values per q at val + q nnz), JU_q at JU + q sJU
 void launch_rs_current(const double2* U, double2* JU, int64_t sJU, int N, const int* rowptr, const int* col,
                        const double2* val, int nnz, int nq, hipStream_t s);
 // part[(q nl + l) n2 + m] = Σ_n r_nm(l) |J_nm(q)|², l < nl, q < nq (J_nm(q) at Jnm + q sJ)
-void launch_rs_pairs(const double2* Jnm, int64_t sJ, int N, const double* E, const double* f, double beta, int nl,
-                     int nq, double* part, hipStream_t s);
+void launch_rs_pairs(const double2* Jnm, int64_t sJ, int N, const double* E, const double* f, const double* g,
+                     double beta, int nl, int nq, double* part, hipStream_t s);
 // out[b] = scale Σ_{k<cnt} in[b cnt + k], b < nout, in a fixed order
 void launch_rs_sum(const double* in, int cnt, int nout, double scale, double* out, hipStream_t s);
 
@@ -373,8 +373,8 @@ void launch_rs_sum(const double* in, int cnt, int nout, double scale, double* ou
 // Most column chunks of the χ'' partials (one partial per chunk, ω and operator)
 constexpr int kOpSpecChunks = 512;
 int op_spec_chunks(int N);   // chunks in use at this N (rows of the partial buffer per operator, each nw long)
-// f_n = logistic(-β E_n), n < 2N
-void launch_op_fermi(const double* E, int N, double beta, double* f, hipStream_t s);
+// f_n = logistic(-β E_n), g_n = logistic(+β E_n), n < 2N
+void launch_op_fermi(const double* E, int N, double beta, double* f, double* g, hipStream_t s);
 // VU_k = Ṽ_k U, k < nops: Ṽ in CSR form (2N rows, columns < 2N, one pattern, nz
 // complex values per operator at val + k nz), VU_k at VU + k sVU
 void launch_op_apply(const double2* U, double2* VU, int64_t sVU, int N, const int* rowptr, const int* col,
@@ -382,8 +382,9 @@ void launch_op_apply(const double2* U, double2* VU, int64_t sVU, int N, const in
 // out[j + nw k] = (η/N) Σ_{n,m} (f_n - f_m) |V_nm(k)|² / ((ω_j - (E_m - E_n))² + η²),
 // ω_j = w_start + j w_step, j < nw, k < nops (V_nm(k) at Vnm + k sV); part:
 // nops x op_spec_chunks(N) x nw
-void launch_op_spec(const double2* Vnm, int64_t sV, int N, const double* E, const double* f, double eta,
-                    double w_start, double w_step, int nw, int nops, double* part, double* out, hipStream_t s);
+void launch_op_spec(const double2* Vnm, int64_t sV, int N, const double* E, const double* f, const double* g,
+                    double beta, double eta, double w_start, double w_step, int nw, int nops, double* part,
+                    double* out, hipStream_t s);
 
 // Eigendecomposition leapfrog step (algo eig; U, JU, rho: nc chains of n2 x n2
 // column-major, E: nc x n2): JU = U diag(logistic(-β E)); after rho = JU U^H,

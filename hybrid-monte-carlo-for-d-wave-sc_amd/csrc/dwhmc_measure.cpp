@@ -82,7 +82,7 @@ int dwh::transport_prepare(dwh_ctx* ctx, int64_t nw, int64_t nd, int slots) {
   }
   if (slots > ctx->tr_slots) {
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (void* q : {(void*)b.U, (void*)b.JU, (void*)b.Jmn, (void*)b.E, (void*)b.f, (void*)b.dia, (void*)b.Wn,
+    for (void* q : {(void*)b.U, (void*)b.JU, (void*)b.Jmn, (void*)b.E, (void*)b.f, (void*)b.g, (void*)b.dia, (void*)b.Wn,
                     (void*)b.wan, (void*)b.w0, (void*)b.lam, (void*)b.dc, (void*)ctx->d_tr_offd, (void*)b.ak,
                     (void*)b.scalars, (void*)ctx->d_tr_info})
       drop_alloc(ctx, q);
@@ -91,7 +91,7 @@ int dwh::transport_prepare(dwh_ctx* ctx, int64_t nw, int64_t nd, int slots) {
     if ((rc = dalloc(ctx, &b.U, m * n2 * n2)) || (rc = dalloc(ctx, &b.JU, m * n2 * n2)) ||
         (rc = dalloc(ctx, &b.Jmn, m * n2 * n2)))
       return rc;
-    for (double** q : {&b.E, &b.f, &b.dia, &b.Wn, &b.wan, &b.w0, &b.lam, &b.dc, &ctx->d_tr_offd})
+    for (double** q : {&b.E, &b.f, &b.g, &b.dia, &b.Wn, &b.wan, &b.w0, &b.lam, &b.dc, &ctx->d_tr_offd})
       if ((rc = dalloc(ctx, q, m * n2))) return rc;
     if ((rc = dalloc(ctx, &b.ak, m * N)) || (rc = dalloc(ctx, &b.scalars, 2 * m)) ||
         (rc = dalloc(ctx, &ctx->d_tr_info, m)))
@@ -134,7 +134,7 @@ dwh::TrBufs tr_slot(const dwh_ctx* ctx, int k) {
   b.U += mat;
   b.JU += mat;
   b.Jmn += mat;
-  for (double** q : {&b.E, &b.f, &b.dia, &b.Wn, &b.wan, &b.w0, &b.lam, &b.dc}) *q += vec;
+  for (double** q : {&b.E, &b.f, &b.g, &b.dia, &b.Wn, &b.wan, &b.w0, &b.lam, &b.dc}) *q += vec;
   b.ak += N * k;
   b.scalars += 2 * k;
   b.sigma += (size_t)std::max<int64_t>(ctx->tr_nw, 0) * k;
@@ -522,6 +522,28 @@ int dwh::eigen_solve(dwh_ctx* ctx, const TrSrc& src, int m) {
   ctx->eig_ph = false;
   ctx->eig_ph_last = 0;   // dwh_info_t::eig_half describes this solve on every exit path
   ctx->eig_quat_last = 0;   // and eig_quat: 0 on the rocSOLVER route and after a zheev re-solve
+  if (ctx->dbg_nstates > 0) {
+    // dwh_debug_set_eigensystem: the staged (E, U) into the slots, once
+    const int ns = ctx->dbg_nstates;
+    const bool ph = ctx->dbg_ph;
+    std::vector<double> Eh;
+    std::vector<double2> Uh;
+    Eh.swap(ctx->dbg_E);
+    Uh.swap(ctx->dbg_U);
+    ctx->dbg_nstates = 0;
+    ctx->dbg_ph = false;
+    if (ns != m)
+      return fail(ctx, DWH_ERR_ARG, "dwh_debug_set_eigensystem staged " + std::to_string(ns) +
+                                        " eigensystems, the eigensolve that followed has " + std::to_string(m) +
+                                        " (staging cleared)");
+    HIPCHECK(ctx, hipMemsetAsync(ctx->d_tr_info, 0, m * sizeof(int), ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(ctx->tr.E, Eh.data(), Eh.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(ctx->tr.U, Uh.data(), Uh.size() * sizeof(double2), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));   // (Eh, Uh leave scope)
+    ctx->eig_ph = ph;
+    ctx->eig_ph_last = ph ? 1 : 0;
+    return DWH_OK;
+  }
   HIPCHECK(ctx, hipMemsetAsync(ctx->d_tr_bad, 0, sizeof(int), ctx->stream));
   if (own) {
     // the own solver (k_eig_orth flags an over-long cluster in d_tr_bad);
@@ -598,7 +620,7 @@ int transport_run(dwh_ctx* ctx, const TrSrc& src, int m, double eta, double dome
   for (int k = 0; k < m; ++k) {
     const dwh::TrBufs b = tr_slot(ctx, k);
     dwh::launch_tr_colstats(b.U, N, (int)ctx->model->Lx, b.E, ctx->beta, eta, ctx->model->t, ctx->model->tp, ctx->d_tr_nbr, b.f,
-                            b.dia, b.Wn, b.wan, b.w0, s);
+                            b.g, b.dia, b.Wn, b.wan, b.w0, s);
     dwh::launch_tr_current(b.U, b.JU, N, ctx->d_tr_rowptr, ctx->d_tr_col, ctx->d_tr_val, ncol, s);
   }
   HIPCHECK(ctx, hipGetLastError());
@@ -1058,14 +1080,14 @@ int response_run(dwh_ctx* ctx, const TrSrc& src, int m, const RsOp& op, int64_t 
   for (int k = 0; k < m; ++k) {
     Scope sc(ctx, T_RESPONSE, 8.0 * n2 * (double)n2 * n2 * nq);
     const dwh::TrBufs b = tr_slot(ctx, k);
-    dwh::launch_rs_colstats(b.U, N, b.E, ctx->beta, op.tb, nbr, b.f, b.dia, s);
+    dwh::launch_rs_colstats(b.U, N, b.E, ctx->beta, op.tb, nbr, b.f, b.g, b.dia, s);
     dwh::launch_rs_sum(b.dia, n2, 1, 1.0 / N, ctx->d_rs_out, s);
     dwh::launch_tr_conj_transpose(b.U, n2, n2, n2, 0, b.Jmn, n2, 0, 1, s);
     for (int64_t q0 = 0; q0 < nq; q0 += g) {
       const int gq = (int)std::min<int64_t>(g, nq - q0);
       dwh::launch_rs_current(b.U, JU, sA, N, rowptr, ctx->d_rs_col, ctx->d_rs_val + q0 * op.nnz, op.nnz, gq, s);
       dwh::gemm_z('N', 'N', n2, n2, n2, one, b.Jmn, n2, 0, JU, n2, sA, zero, Jnm, n2, sA, gq, s);
-      dwh::launch_rs_pairs(Jnm, sA, N, b.E, b.f, ctx->beta, (int)nl, gq, ctx->d_rs_part, s);
+      dwh::launch_rs_pairs(Jnm, sA, N, b.E, b.f, b.g, ctx->beta, (int)nl, gq, ctx->d_rs_part, s);
       dwh::launch_rs_sum(ctx->d_rs_part, n2, gq * (int)nl, 1.0 / N, ctx->d_rs_out + 1 + q0 * nl, s);
     }
     HIPCHECK(ctx, hipGetLastError());
@@ -1213,18 +1235,18 @@ int operator_run(dwh_ctx* ctx, const TrSrc& src, int m, const OpNambu& op, int64
   for (int k = 0; k < m; ++k) {
     Scope sc(ctx, T_OPERATOR, 8.0 * n2 * (double)n2 * n2 * nops);
     const dwh::TrBufs b = tr_slot(ctx, k);
-    dwh::launch_op_fermi(b.E, N, ctx->beta, b.f, s);
+    dwh::launch_op_fermi(b.E, N, ctx->beta, b.f, b.g, s);
     dwh::launch_tr_conj_transpose(b.U, n2, n2, n2, 0, b.Jmn, n2, 0, 1, s);
     for (int64_t k0 = 0; k0 < nops; k0 += g) {
       const int gk = (int)std::min<int64_t>(g, nops - k0);
       dwh::launch_op_apply(b.U, VU, sA, N, ctx->d_rs_idx, ctx->d_rs_col, ctx->d_rs_val + k0 * op.nz, op.nz, gk, s);
       dwh::gemm_z('N', 'N', n2, n2, n2, one, b.Jmn, n2, 0, VU, n2, sA, zero, Vnm, n2, sA, gk, s);
       if (nl > 0) {
-        dwh::launch_rs_pairs(Vnm, sA, N, b.E, b.f, ctx->beta, (int)nl, gk, ctx->d_rs_part, s);
+        dwh::launch_rs_pairs(Vnm, sA, N, b.E, b.f, b.g, ctx->beta, (int)nl, gk, ctx->d_rs_part, s);
         dwh::launch_rs_sum(ctx->d_rs_part, n2, gk * (int)nl, 1.0 / N, d_chi + k0 * nl, s);
       }
       if (nw > 0)
-        dwh::launch_op_spec(Vnm, sA, N, b.E, b.f, eta, w_start, w_step, (int)nw, gk, ctx->d_op_part,
+        dwh::launch_op_spec(Vnm, sA, N, b.E, b.f, b.g, ctx->beta, eta, w_start, w_step, (int)nw, gk, ctx->d_op_part,
                             d_chi2 + k0 * nw, s);
     }
     HIPCHECK(ctx, hipGetLastError());
@@ -1314,6 +1336,44 @@ int dwh_eigensystem(dwh_ctx* ctx, int64_t chain, double* E, dwh_c128* U) {
     HIPCHECK(ctx, hipMemcpyAsync(U, ctx->tr.U, n2 * n2 * sizeof(double2), hipMemcpyDeviceToHost,
                                  ctx->stream));
   return eigen_info_check(ctx, 1);
+}
+
+int dwh_debug_set_eigensystem(dwh_ctx* ctx, int64_t nstates, const double* E, const dwh_c128* U, int32_t ph) {
+  if (!ctx) return fail(nullptr, DWH_ERR_ARG, "NULL context");
+  ctx->dbg_nstates = 0;   // a refused call leaves nothing staged
+  ctx->dbg_E.clear();
+  ctx->dbg_U.clear();
+  if (!E || !U) return fail(ctx, DWH_ERR_ARG, "NULL argument (E or U)");
+  const int64_t cap = tr_group(ctx, INT32_MAX);
+  if (nstates < 1 || nstates > cap)
+    return fail(ctx, DWH_ERR_ARG, "nstates must be in [1, " + std::to_string(cap) + "] (the slots of one eigensolve)");
+  const int64_t n2 = 2 * (int64_t)ctx->d.N;
+  for (int64_t k = 0; k < nstates; ++k) {
+    const double* e = E + k * n2;
+    double emax = 0.0;
+    for (int64_t n = 0; n < n2; ++n) {
+      if (!std::isfinite(e[n])) return fail(ctx, DWH_ERR_ARG, "non-finite eigenvalue in state " + std::to_string(k));
+      if (n > 0 && e[n] < e[n - 1])
+        return fail(ctx, DWH_ERR_ARG, "eigenvalues of state " + std::to_string(k) + " are not ascending at " +
+                                          std::to_string(n));
+      emax = std::max(emax, std::fabs(e[n]));
+    }
+    if (ph)
+      for (int64_t n = 0; n < n2; ++n)
+        if (std::fabs(e[n] + e[n2 - 1 - n]) > 1e-12 * (1.0 + emax))
+          return fail(ctx, DWH_ERR_ARG, "ph: E[n] + E[2N-1-n] of state " + std::to_string(k) + " is not zero at " +
+                                            std::to_string(n));
+  }
+  const int64_t nu = nstates * n2 * n2;
+  for (int64_t i = 0; i < nu; ++i)
+    if (!std::isfinite(U[i].re) || !std::isfinite(U[i].im))
+      return fail(ctx, DWH_ERR_ARG, "non-finite eigenvector entry");
+  ctx->dbg_E.assign(E, E + nstates * n2);
+  ctx->dbg_U.resize((size_t)nu);
+  for (int64_t i = 0; i < nu; ++i) ctx->dbg_U[(size_t)i] = make_double2(U[i].re, U[i].im);
+  ctx->dbg_nstates = (int)nstates;
+  ctx->dbg_ph = ph != 0;
+  return DWH_OK;
 }
 
 int dwh_measure_transport(dwh_ctx* ctx, int64_t chain, double eta, double domega, double omega_max,

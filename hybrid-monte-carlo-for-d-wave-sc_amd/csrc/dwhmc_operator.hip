@@ -19,6 +19,7 @@
 //   k_op_spec_sum  the chunks added in a fixed order, times η/N
 // All plain fp64 VALU, every sum in a fixed order (no atomics).  Matrices are
 // column-major with leading dimension n2 = 2N, as in dwhmc_transport.hip.
+#include "dwhmc_device.h"
 #include "dwhmc_internal.h"
 
 namespace dwh {
@@ -33,9 +34,12 @@ __device__ inline double logistic_d(double x) {
   return e / (1.0 + e);
 }
 
-__global__ void k_op_fermi(const double* __restrict__ E, int n2, double beta, double* __restrict__ f) {
+__global__ void k_op_fermi(const double* __restrict__ E, int n2, double beta, double* __restrict__ f,
+                           double* __restrict__ g) {
   const int n = blockIdx.x * kTB + threadIdx.x;
-  if (n < n2) f[n] = logistic_d(-beta * E[n]);
+  if (n >= n2) return;
+  f[n] = logistic_d(-beta * E[n]);
+  g[n] = logistic_d(beta * E[n]);   // 1 - f_n from its own exponential
 }
 
 // VU_k = Ṽ_k U for the operators k of a group (blockIdx.z): Ṽ in CSR form with
@@ -61,10 +65,6 @@ __global__ void k_op_apply(const double2* __restrict__ U, double2* __restrict__ 
   VU[(size_t)k * sVU + (size_t)n * n2 + r] = acc;
 }
 
-__device__ inline double grid_point(double start, double step, int k) {
-  return __dadd_rn(start, __dmul_rn(step, (double)k));
-}
-
 // v_rcp_f64 + one Newton step (<= ~11 ulp), as k_tr_sigma.  The χ'' terms
 // carry both signs, so the error bound is relative to Σ |c_nm| / ((ω - ΔE)² +
 // η²), not to χ'' itself: a few ulp of the absolute sum.
@@ -84,8 +84,8 @@ __device__ inline double rcp_nr1(double p) {
 // c = 0, ΔE = 0: their denominator ω² + η² > 0.
 __global__ void __launch_bounds__(kTB)
 k_op_spec(const double2* __restrict__ Vnm, int64_t sV, int n2, const double* __restrict__ E,
-          const double* __restrict__ f, double eta, double w_start, double w_step, int nw, int cols,
-          double* __restrict__ part) {
+          const double* __restrict__ f, const double* __restrict__ g, double beta, double eta, double w_start,
+          double w_step, int nw, int cols, double* __restrict__ part) {
   __shared__ double sdE[kTB], sc[kTB];
   const int tid = threadIdx.x;
   const int j = blockIdx.x * kTB + tid;
@@ -95,16 +95,19 @@ k_op_spec(const double2* __restrict__ Vnm, int64_t sV, int n2, const double* __r
   const double2* V = Vnm + (size_t)blockIdx.z * sV;
   double acc0 = 0, acc1 = 0;
   for (int m = m0; m < m1; ++m) {
-    const double Em = E[m], fm = f[m];
+    const double Em = E[m], fm = f[m], gm = g[m];
     const double2* colm = V + (size_t)m * n2;
     for (int n0 = 0; n0 < n2; n0 += kTB) {
       const int n = n0 + tid;
       double c = 0.0, dE = 0.0;
       if (n < n2) {
-        const double df = f[n] - fm;
+        // (fermi_diff, dwhmc_device.h: f_n - f_m without the cancellation of two
+        // levels on one side of the Fermi level)
+        const double d = Em - E[n];
+        const double df = fermi_diff(d, f[n], g[n], fm, gm, beta);
         if (fabs(df) >= 1e-12) {
           const double2 v = colm[n];
-          dE = Em - E[n];
+          dE = d;
           c = df * (v.x * v.x + v.y * v.y);
         }
       }
@@ -161,8 +164,8 @@ int op_spec_chunks(int N) {
   return used;
 }
 
-void launch_op_fermi(const double* E, int N, double beta, double* f, hipStream_t s) {
-  hipLaunchKernelGGL(k_op_fermi, dim3(cdiv(2 * N, kTB)), dim3(kTB), 0, s, E, 2 * N, beta, f);
+void launch_op_fermi(const double* E, int N, double beta, double* f, double* g, hipStream_t s) {
+  hipLaunchKernelGGL(k_op_fermi, dim3(cdiv(2 * N, kTB)), dim3(kTB), 0, s, E, 2 * N, beta, f, g);
 }
 
 void launch_op_apply(const double2* U, double2* VU, int64_t sVU, int N, const int* rowptr, const int* col,
@@ -172,13 +175,14 @@ void launch_op_apply(const double2* U, double2* VU, int64_t sVU, int N, const in
                      val, nz);
 }
 
-void launch_op_spec(const double2* Vnm, int64_t sV, int N, const double* E, const double* f, double eta,
-                    double w_start, double w_step, int nw, int nops, double* part, double* out, hipStream_t s) {
+void launch_op_spec(const double2* Vnm, int64_t sV, int N, const double* E, const double* f, const double* g,
+                    double beta, double eta, double w_start, double w_step, int nw, int nops, double* part,
+                    double* out, hipStream_t s) {
   if (nops <= 0 || nw <= 0) return;
   int cols, used;
   spec_split(N, &cols, &used);
-  hipLaunchKernelGGL(k_op_spec, dim3(cdiv(nw, kTB), used, nops), dim3(kTB), 0, s, Vnm, sV, 2 * N, E, f, eta, w_start,
-                     w_step, nw, cols, part);
+  hipLaunchKernelGGL(k_op_spec, dim3(cdiv(nw, kTB), used, nops), dim3(kTB), 0, s, Vnm, sV, 2 * N, E, f, g, beta, eta,
+                     w_start, w_step, nw, cols, part);
   hipLaunchKernelGGL(k_op_spec_sum, dim3(cdiv(nw, 64), nops), dim3(256), 0, s, part, used, nw, eta / N, out);
 }
 

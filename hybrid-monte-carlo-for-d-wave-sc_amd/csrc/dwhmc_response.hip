@@ -12,6 +12,7 @@
 // All plain fp64 VALU; every sum has a fixed order (no atomics), so results
 // are the same run to run.  Matrices are column-major with leading dimension
 // n2 = 2N, as in dwhmc_transport.hip.
+#include "dwhmc_device.h"
 #include "dwhmc_internal.h"
 
 namespace dwh {
@@ -43,14 +44,15 @@ __device__ inline void block_sum(double (&v)[NV], double (*sh)[kTB]) {
   }
 }
 
-// Per eigenstate n (one block per column of U): f_n = logistic(-β E_n) and
+// Per eigenstate n (one block per column of U): f_n = logistic(-β E_n),
+// g_n = 1 - f_n = logistic(+β E_n) (its own exponential: no cancellation) and
 //   dia_n = [E_n > 0] w_n tanh(β E_n / 2),
 //   w_n = Σ_i Σ_b t_b 2 Re(v_i conj(v_j) - conj(u_i) u_j),  j = nbr[b][i]
 // (src/Observables.jl:345-362 with the bond list of the direction: nbr 3 x N,
 // hopping tb[b]); k_tr_colstats' dia for the x list.
 __global__ void k_rs_colstats(const double2* __restrict__ U, int n2, int N, const double* __restrict__ E, double beta,
                               double t0, double t1, double t2, const int* __restrict__ nbr, double* __restrict__ f,
-                              double* __restrict__ dia) {
+                              double* __restrict__ g, double* __restrict__ dia) {
   __shared__ double sh[1][kTB];
   const int n = blockIdx.x;
   const double2* u = U + (size_t)n * n2;
@@ -72,6 +74,7 @@ __global__ void k_rs_colstats(const double2* __restrict__ U, int n2, int N, cons
   if (threadIdx.x == 0) {
     const double e = E[n];
     f[n] = logistic_d(-beta * e);
+    g[n] = logistic_d(beta * e);
     dia[n] = e > 0 ? sh[0][0] * tanh(0.5 * beta * e) : 0.0;
   }
 }
@@ -103,14 +106,16 @@ __global__ void k_rs_current(const double2* __restrict__ U, double2* __restrict_
 //   l = 0:  r = (f_n - f_m)/(E_m - E_n), β f_n (1 - f_n) where |E_m - E_n| < 1e-8
 //           (the reference's rule, src/Observables.jl:370-381)
 //   l >= 1: r = (f_n - f_m)(E_m - E_n) / ((E_m - E_n)² + Ω_l²), Ω_l = 2π l / β
+// with 1 - f_n = g_n and f_n - f_m = fermi_diff (dwhmc_device.h): neither cancels
 template <int NL>
 __global__ void __launch_bounds__(kTB)
 k_rs_pairs(const double2* __restrict__ Jnm, int64_t sJ, int n2, const double* __restrict__ E,
-           const double* __restrict__ f, double beta, int l0, int nl, double* __restrict__ part) {
+           const double* __restrict__ f, const double* __restrict__ g, double beta, int l0, int nl,
+           double* __restrict__ part) {
   __shared__ double sh[NL][kTB];
   const int m = blockIdx.x, q = blockIdx.y;
   const double2* colm = Jnm + (size_t)q * sJ + (size_t)m * n2;
-  const double Em = E[m], fm = f[m];
+  const double Em = E[m], fm = f[m], gm = g[m];
   double om2[NL], acc[NL];
 #pragma unroll
   for (int k = 0; k < NL; ++k) {
@@ -121,12 +126,12 @@ k_rs_pairs(const double2* __restrict__ Jnm, int64_t sJ, int n2, const double* __
   for (int n = threadIdx.x; n < n2; n += kTB) {
     const double2 j = colm[n];
     const double J2 = j.x * j.x + j.y * j.y;
-    const double dE = Em - E[n], fn = f[n], df = fn - fm;
+    const double dE = Em - E[n], fn = f[n], gn = g[n], df = fermi_diff(dE, fn, gn, fm, gm, beta);
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
       if (l0 + k >= nl) break;   // (uniform: the last chunk's unused accumulators)
       double r;
-      if (l0 + k == 0) r = fabs(dE) < 1e-8 ? beta * fn * (1.0 - fn) : df / dE;
+      if (l0 + k == 0) r = fabs(dE) < 1e-8 ? beta * fn * gn : df / dE;
       else r = df * dE / (dE * dE + om2[k]);
       acc[k] += r * J2;
     }
@@ -154,9 +159,9 @@ inline int cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
 }  // namespace
 
 void launch_rs_colstats(const double2* U, int N, const double* E, double beta, const double* tb, const int* nbr,
-                        double* f, double* dia, hipStream_t s) {
+                        double* f, double* g, double* dia, hipStream_t s) {
   hipLaunchKernelGGL(k_rs_colstats, dim3(2 * N), dim3(kTB), 0, s, U, 2 * N, N, E, beta, tb[0], tb[1], tb[2], nbr, f,
-                     dia);
+                     g, dia);
 }
 
 void launch_rs_current(const double2* U, double2* JU, int64_t sJU, int N, const int* rowptr, const int* col,
@@ -166,16 +171,16 @@ void launch_rs_current(const double2* U, double2* JU, int64_t sJU, int N, const 
                      col, val, nnz);
 }
 
-void launch_rs_pairs(const double2* Jnm, int64_t sJ, int N, const double* E, const double* f, double beta, int nl,
-                     int nq, double* part, hipStream_t s) {
+void launch_rs_pairs(const double2* Jnm, int64_t sJ, int N, const double* E, const double* f, const double* g,
+                     double beta, int nl, int nq, double* part, hipStream_t s) {
   if (nq <= 0) return;
   const int n2 = 2 * N;
   for (int l0 = 0; l0 < nl; l0 += kRsLChunk) {
     const dim3 grid(n2, nq);
     if (nl - l0 == 1)   // (the Ω = 0 call: one accumulator)
-      hipLaunchKernelGGL(k_rs_pairs<1>, grid, dim3(kTB), 0, s, Jnm, sJ, n2, E, f, beta, l0, nl, part);
+      hipLaunchKernelGGL(k_rs_pairs<1>, grid, dim3(kTB), 0, s, Jnm, sJ, n2, E, f, g, beta, l0, nl, part);
     else
-      hipLaunchKernelGGL(k_rs_pairs<kRsLChunk>, grid, dim3(kTB), 0, s, Jnm, sJ, n2, E, f, beta, l0, nl, part);
+      hipLaunchKernelGGL(k_rs_pairs<kRsLChunk>, grid, dim3(kTB), 0, s, Jnm, sJ, n2, E, f, g, beta, l0, nl, part);
   }
 }
 

@@ -35,11 +35,6 @@ constexpr int kMaxDft = 1024;   // longest lattice side with its twiddles in LDS
 
 inline int cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
 
-// point k of a float range, as the DOS kernel of dwhmc_transport.hip forms it
-__device__ inline double grid_point(double start, double step, int64_t k) {
-  return __dadd_rn(start, __dmul_rn(step, (double)k));
-}
-
 // Λ[n, q] = L(ω_q - E_n) at Lam[q + ldq n] for q < cnt, n < n2; ω_q = point
 // first + q stride of the grid d0 + k dw; state s = blockIdx.z
 __global__ void __launch_bounds__(kTB)

@@ -14,6 +14,7 @@
 // LDS (one broadcast read per pair per wave), writing one partial per (chunk,
 // ω); a second kernel adds the chunks in a fixed order, so results are
 // deterministic run to run.
+#include "dwhmc_device.h"
 #include "dwhmc_internal.h"
 
 namespace dwh {
@@ -74,6 +75,8 @@ __global__ void k_tr_assemble(double2* __restrict__ A, int n2, int N, const int*
 
 // Per eigenstate n (one block per column of U):
 //   f_n = logistic(-β E_n)                                   (compute_forces!, :50)
+//   g_n = 1 - f_n = logistic(+β E_n), from its own exponential (1.0 - f_n
+//         loses eps / g_n below the Fermi level)
 //   dia_n = [E_n > 0] w_n tanh(β E_n / 2), w_n the x-bond kinetic weight  (:345-362)
 //   Wn_n = Σ_i |u_i|^2                                        (DOS weight, :452-456)
 //   wan_n = (|Σ_i (-1)^x u_i|^2 + |Σ_i (-1)^y u_i|^2) / 2N     (antinodal, :465-488)
@@ -82,7 +85,7 @@ __global__ void k_tr_assemble(double2* __restrict__ A, int n2, int N, const int*
 __global__ void k_tr_colstats(const double2* __restrict__ U, int n2, int N, int Lx,
                               const double* __restrict__ E, double beta, double eta, double t,
                               double tp, const int* __restrict__ nbr, double* __restrict__ f,
-                              double* __restrict__ dia, double* __restrict__ Wn,
+                              double* __restrict__ g, double* __restrict__ dia, double* __restrict__ Wn,
                               double* __restrict__ wan, double* __restrict__ w0) {
   __shared__ double sh[6][kTB];
   const int n = blockIdx.x;
@@ -113,6 +116,7 @@ __global__ void k_tr_colstats(const double2* __restrict__ U, int n2, int N, int 
   if (threadIdx.x == 0) {
     const double e = E[n];
     f[n] = logistic_d(-beta * e);
+    g[n] = logistic_d(beta * e);
     dia[n] = e > 0 ? sh[0][0] * tanh(0.5 * beta * e) : 0.0;
     Wn[n] = sh[1][0];
     wan[n] = 0.5 * (sh[2][0] * sh[2][0] + sh[3][0] * sh[3][0] + sh[4][0] * sh[4][0] +
@@ -146,18 +150,18 @@ __global__ void k_tr_current(const double2* __restrict__ U, double2* __restrict_
 // Per column m of J_mn (threads over n): the paramagnetic sum Λ (:366-384)
 // and the DC conductivity (:405-413), before the 1/N (and π·(1/π)) factors.
 __global__ void k_tr_pairs(const double2* __restrict__ Jmn, int n2, const double* __restrict__ E,
-                           const double* __restrict__ f, double beta, double eta,
-                           double* __restrict__ lam_part, double* __restrict__ dc_part) {
+                           const double* __restrict__ f, const double* __restrict__ g, double beta,
+                           double eta, double* __restrict__ lam_part, double* __restrict__ dc_part) {
   __shared__ double sh[2][kTB];
   const int m = blockIdx.x;
-  const double Em = E[m], fm = f[m], eta2 = eta * eta;
+  const double Em = E[m], fm = f[m], gm = g[m], eta2 = eta * eta;
   double acc[2] = {0, 0};
   for (int n = threadIdx.x; n < n2; n += kTB) {
     const double2 j = Jmn[(size_t)m * n2 + n];
     const double J2 = j.x * j.x + j.y * j.y;
-    const double dE = Em - E[n], fn = f[n];
-    const double bf = beta * fn * (1.0 - fn);
-    const double ratio = fabs(dE) < 1e-8 ? bf : (fn - fm) / dE;
+    const double dE = Em - E[n], fn = f[n], gn = g[n];
+    const double bf = beta * fn * gn;
+    const double ratio = fabs(dE) < 1e-8 ? bf : fermi_diff(dE, fn, gn, fm, gm, beta) / dE;
     acc[0] += ratio * J2;
     acc[1] += bf * J2 * (eta / (dE * dE + eta2));
   }
@@ -166,10 +170,6 @@ __global__ void k_tr_pairs(const double2* __restrict__ Jmn, int n2, const double
     lam_part[m] = sh[0][0];
     dc_part[m] = sh[1][0];
   }
-}
-
-__device__ inline double grid_point(double start, double step, int k) {
-  return __dadd_rn(start, __dmul_rn(step, (double)k));
 }
 
 // σ(ω) partials (:415-423).  The reference sums c_nm L(ω - ΔE_nm) / ω over all
@@ -197,8 +197,8 @@ __device__ inline double rcp_nr1(double p) {
 // (n2-1-m, n2-1-n)), the self-partnered m = n2-1-n once.
 __global__ void __launch_bounds__(kTB)
 k_tr_sigma(const double2* __restrict__ Jmn, int n2, const double* __restrict__ E,
-           const double* __restrict__ f, double eta, double w_start, double w_step, int nw,
-           int rows, int nrow, int ph, double* __restrict__ part) {
+           const double* __restrict__ f, const double* __restrict__ g, double beta, double eta,
+           double w_start, double w_step, int nw, int rows, int nrow, int ph, double* __restrict__ part) {
   __shared__ double sdE[kTB], scd[kTB];
   const int tid = threadIdx.x;
   const int k = blockIdx.x * kTB + tid;
@@ -207,17 +207,20 @@ k_tr_sigma(const double2* __restrict__ Jmn, int n2, const double* __restrict__ E
   const int n0 = blockIdx.y * rows, n1 = min(n0 + rows, nrow);
   double acc0 = 0, acc1 = 0;
   for (int n = n0; n < n1; ++n) {
-    const double En = E[n], fn = f[n];
+    const double En = E[n], fn = f[n], gn = g[n];
     const double2* col = Jmn + (size_t)n * n2;
     const int mend = ph ? n2 - 1 - n : n2 - 1;   // last m of row n
     for (int m0 = ((n + 1) / kTB) * kTB; m0 <= mend; m0 += kTB) {
       const int m = m0 + tid;
       double cd = 0.0, dE = 0.0;
       if (m > n && m <= mend) {
-        const double df = fn - f[m];
+        // (fermi_diff: two levels on one side of the Fermi level differ by far
+        // less than either f, and their pairs are the resonant ones at small ω)
+        const double d = E[m] - En;
+        const double df = fermi_diff(d, fn, gn, f[m], g[m], beta);
         if (fabs(df) >= 1e-12) {
           const double2 j = col[m];
-          dE = E[m] - En;
+          dE = d;
           cd = df * (j.x * j.x + j.y * j.y) * dE;
           if (ph && m < mend) cd *= 2.0;
         }
@@ -505,10 +508,10 @@ void launch_tr_assemble(double2* A, int N, const int* hcol, const double* hval, 
 }
 
 void launch_tr_colstats(const double2* U, int N, int Lx, const double* E, double beta, double eta,
-                        double t, double tp, const int* nbr, double* f, double* dia, double* Wn,
+                        double t, double tp, const int* nbr, double* f, double* g, double* dia, double* Wn,
                         double* wan, double* w0, hipStream_t s) {
   hipLaunchKernelGGL(k_tr_colstats, dim3(2 * N), dim3(kTB), 0, s, U, 2 * N, N, Lx, E, beta, eta, t,
-                     tp, nbr, f, dia, Wn, wan, w0);
+                     tp, nbr, f, g, dia, Wn, wan, w0);
 }
 
 void launch_tr_current(const double2* U, double2* JU, int N, const int* rowptr, const int* col,
@@ -532,13 +535,13 @@ void launch_tr_reduce(const TrBufs& b, int N, int Lx, int Ly, double beta, doubl
                       const TrGrid& g, bool ph, hipStream_t s) {
   const int n2 = 2 * N;
   const int npair = ph ? N : n2;   // columns of J_mn the pair sums read
-  hipLaunchKernelGGL(k_tr_pairs, dim3(npair), dim3(kTB), 0, s, b.Jmn, n2, b.E, b.f, beta, eta, b.lam,
-                     b.dc);
+  hipLaunchKernelGGL(k_tr_pairs, dim3(npair), dim3(kTB), 0, s, b.Jmn, n2, b.E, b.f, b.g, beta, eta,
+                     b.lam, b.dc);
   if (g.nw > 0) {
     const int nchunk = std::min(tr_sigma_chunks(N), npair), rows = cdiv(npair, nchunk);
     const int used = cdiv(npair, rows);
     hipLaunchKernelGGL(k_tr_sigma, dim3(cdiv(g.nw, kTB), used), dim3(kTB), 0, s, b.Jmn, n2, b.E,
-                       b.f, eta, g.w0, g.dw, g.nw, rows, npair, (int)ph, b.part);
+                       b.f, b.g, beta, eta, g.w0, g.dw, g.nw, rows, npair, (int)ph, b.part);
     hipLaunchKernelGGL(k_tr_sigma_sum, dim3(cdiv(g.nw, 64)), dim3(256), 0, s, b.part, used, g.nw,
                        eta, N, b.sigma);
   }

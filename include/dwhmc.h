@@ -447,6 +447,24 @@ int dwh_debug_dense_H(dwh_ctx* ctx, int64_t chain, dwh_c128* H);
  * `chain`) ascending into E, the site-by-site reduction's device time into
  * *ms (nullable). */
 int dwh_debug_qeig(dwh_ctx* ctx, int64_t chain, double* E, double* ms);
+
+/* Eigensystem injection (tests of the measurement reductions; debug only).
+ * Stages nstates eigensystems on the host: E holds 2N values per state,
+ * ascending; U is 2N x 2N column-major per state, column n belonging to E[n]
+ * (U need not diagonalise anything).  The next eigensolve of this context
+ * with exactly nstates matrices — the one dwh_measure_transport(_deltas),
+ * dwh_measure_spectral_maps, dwh_measure_current_response and
+ * dwh_measure_operator_response run after preparing their buffers — copies
+ * them into its slots instead of solving, reports the solve as particle-hole
+ * closed (dwh_info_t::eig_half) iff ph != 0 and as not structure-preserving
+ * (eig_quat = 0), and clears the staging: the injection is one-shot.  With
+ * ph != 0 transport takes its half-pair sums, so column 2N-1-n of U must be
+ * the Nambu partner (-conj(v); conj(u)) of column n = (u; v) up to a phase.
+ * DWH_ERR_ARG (nothing staged) for NULL arguments, a non-finite E or U, E not
+ * ascending, nstates outside [1, the slots of one eigensolve], and with ph
+ * |E[n] + E[2N-1-n]| > 1e-12 (1 + max|E|).  A next eigensolve with another
+ * number of matrices fails with DWH_ERR_ARG and clears the staging too. */
+int dwh_debug_set_eigensystem(dwh_ctx* ctx, int64_t nstates, const double* E, const dwh_c128* U, int32_t ph);
 int dwh_debug_level0(dwh_ctx* ctx, int64_t chain, int64_t pole, int32_t refill, dwh_c128* M, double* y);
 
 /* ---- CR kernel and per-pole test entries (not on the step path) -----------
