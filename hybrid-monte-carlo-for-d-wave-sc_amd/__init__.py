@@ -5,7 +5,8 @@ Layout:
   _lib.py    ctypes binding of the ABI
   context.py FermionContext: batched device handle
   hmc.py     the reference's hot-path API (ModelParameters ... hmc_sweep)
-  vertices.py sparse one-body vertices for measure_operator_response (host numpy)
+  vertices.py sparse one-body vertices for measure_operator_response and Nambu
+              vertices for measure_nambu_response (host numpy)
   simulation.py run_simulation (src/Simulation.jl): adaptive Nt, log, observables.csv
   replicas.py one-process-per-GPU replica driver (RCCL only gathers observables)
 

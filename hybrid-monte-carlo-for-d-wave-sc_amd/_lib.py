@@ -97,6 +97,9 @@ SIGNATURES = {
     "dwh_measure_operator_response": (C.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _D, _D, _D,
                                                 _I64, _P]),
     "dwh_debug_operator_nambu": (C.c_int, [_I64, _I64, _P, _P, _I64, _P, _P, _P]),
+    "dwh_measure_nambu_response": (C.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _D, _D,
+                                             _D, _I64, _P]),
+    "dwh_debug_nambu_dense": (C.c_int, [_I64, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
     "dwh_debug_dense_H": (C.c_int, [_P, _I64, _P]),
     "dwh_debug_qeig": (C.c_int, [_P, _I64, _P, _P]),
     "dwh_debug_set_eigensystem": (C.c_int, [_P, _I64, _P, _P, _I32]),

@@ -397,6 +397,77 @@ class FermionContext:
             return dict(chi=chi[0], chi2=chi2[0], omega=grid)
         return dict(chi=chi, chi2=chi2, omega=grid)
 
+    def measure_nambu_response(self, vertices, pairs=None, n_matsubara: int = 1, omega=None, eta=None,
+                               chain: int = 0, deltas=None) -> dict:
+        """Cross response <O_a ; O_b†> of general Nambu vertices, pairing parts
+        included (dwh_measure_nambu_response): O_k = Ψ† W_k Ψ with W_k any
+        complex 2N x 2N matrix in the basis Ψ = (c_{i↑}; c†_{i↓}).
+        vertices: a tuple (rowptr, col, val) — one CSR pattern with 2N rows
+        (rowptr an integer array of 2N + 1 entries, which is what tells it
+        from a collection) and val (nops, nnz) — or a list or tuple of
+        vertices, each a vertices.NambuVertex, a vertices.Vertex (lifted to
+        V ⊕ (-s V^T)), a COO triple over 2N or a dense (2N, 2N) matrix; one
+        NambuVertex / Vertex may be passed bare.  pairs: list of (a, b)
+        indices into the vertices (None: every (k, k)).  omega / eta / chain / deltas as in
+        measure_operator_response.  Returns complex chi ((nstates,) npairs,
+        n_matsubara) = Σ (f_n - f_m)/(ΔE - iΩ_l) X^a conj(X^b) / N with the
+        l = 0 rules of measure_current_response, complex chi2 ((nstates,)
+        npairs, n_w), omega (n_w,) and pairs (npairs, 2)."""
+        from . import vertices as vx
+        N = self.N
+        if isinstance(vertices, (vx.NambuVertex, vx.Vertex)):
+            vertices = [vertices]                                  # one vertex passed bare
+        # a CSR tuple is told by its content: an integer rowptr of 2N + 1 entries first
+        first = vertices[0] if isinstance(vertices, tuple) and len(vertices) == 3 else None
+        if first is not None and not isinstance(first, (tuple, list)) and np.ndim(first) == 1 \
+                and len(first) == 2 * N + 1 and np.issubdtype(np.asarray(first).dtype, np.integer):
+            rowptr = np.ascontiguousarray(vertices[0], dtype=np.int64).ravel()
+            col = np.ascontiguousarray(vertices[1], dtype=np.int64).ravel()
+            val = np.ascontiguousarray(np.atleast_2d(np.asarray(vertices[2], dtype=np.complex128)))
+            if val.ndim != 2 or val.shape[1] != len(col):
+                raise ValueError(f"vertices: a CSR tuple needs val (nops, {len(col)})")
+        else:
+            vertices = list(vertices)
+            if not vertices:
+                raise ValueError("vertices is empty")
+            rowptr, col, val = vx.union_csr_nambu(vertices, N)
+        nops, nnz = val.shape
+        if pairs is None:
+            pr = np.stack([np.arange(nops, dtype=np.int64)] * 2, axis=1)
+        else:
+            pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        pr = np.ascontiguousarray(pr)
+        npairs = pr.shape[0]
+        nl = int(n_matsubara)
+        if omega is None:
+            w0, dw, nw = 0.0, 0.0, 0
+        else:
+            if isinstance(omega, dict):
+                extra = set(omega) - {"start", "step", "count"}
+                if extra:
+                    raise ValueError(f"omega: unknown keys {sorted(extra)}")
+                omega = (omega["start"], omega["step"], omega["count"])
+            w0, dw, nw = float(omega[0]), float(omega[1]), int(omega[2])
+            if eta is None:
+                raise ValueError("eta is needed with omega")
+        D, ns = None, 1
+        if deltas is not None:
+            Dl = np.asarray(deltas, dtype=np.complex128)
+            if Dl.ndim != 3 or Dl.shape[1:] != (N, 2) or Dl.shape[0] < 1:
+                raise ValueError(f"expected (nstates, {N}, 2) pairing fields")
+            ns = Dl.shape[0]
+            D = np.ascontiguousarray(np.transpose(Dl, (0, 2, 1)))
+        chi = np.empty((ns, npairs, max(nl, 0)), dtype=np.complex128)
+        chi2 = np.empty((ns, npairs, max(nw, 0)), dtype=np.complex128)
+        self._c(self._lib.dwh_measure_nambu_response(
+            self._h, int(chain), ns, ptr(D), nops, ptr(rowptr), ptr(col), nnz, ptr(val), npairs, ptr(pr), nl,
+            ptr(chi) if nl > 0 else None, 0.0 if eta is None else float(eta), w0, dw, nw,
+            ptr(chi2) if nw > 0 else None))
+        grid = w0 + dw * np.arange(max(nw, 0))
+        if deltas is None:
+            return dict(chi=chi[0], chi2=chi2[0], omega=grid, pairs=pr)
+        return dict(chi=chi, chi2=chi2, omega=grid, pairs=pr)
+
     # -- assembly read-back (parity tests) --------------------------------
     def debug_dense_H(self, chain: int = 0) -> np.ndarray:
         """H_BdG(Δ) (2N, 2N) as the eigen/transport path assembles it (dwh_debug_dense_H)."""
@@ -450,7 +521,8 @@ class FermionContext:
 
     # -- timing ----------------------------------------------------------
     TIMERS =("gj_update", "gj_pivot", "assemble", "contract", "step", "gj_edge", "cr_gemm", "cr_inv",
-              "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral", "response", "operator")
+              "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral", "response", "operator",
+              "nambu")
 
     def timing_enable(self, on=True):
         """on: True (all timers), False, or an iterable of timer names."""

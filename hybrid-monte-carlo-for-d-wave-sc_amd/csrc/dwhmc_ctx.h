@@ -22,7 +22,7 @@ namespace dwh {
 
 enum TimerName {
   T_GJ_UPDATE = 0, T_GJ_PIVOT, T_ASSEMBLE, T_CONTRACT, T_STEP, T_GJ_EDGE, T_CR_GEMM, T_CR_INV, T_CR_INVSIDE,
-  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_OPERATOR, T_COUNT
+  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_OPERATOR, T_NAMBU, T_COUNT
 };
 inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assemble", "contract",
                                                  "step",      "gj_edge",  "cr_gemm",  "cr_inv",
@@ -31,7 +31,8 @@ inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assem
                                                  "cr_sparse",
                                                  "spectral",    // LDOS / A(k, ω) map stage (work: flops)
                                                  "response",    // Λ(q, iΩ) after its eigensolve (work: flops)
-                                                 "operator"};   // χ(iΩ), χ''(ω) of sparse vertices after their eigensolve (work: flops)
+                                                 "operator",    // χ(iΩ), χ''(ω) of sparse vertices after their eigensolve (work: flops)
+                                                 "nambu"};      // cross response of Nambu vertices after its eigensolve (work: flops)
 
 enum Algo { ALGO_DENSE = 0, ALGO_CR = 1, ALGO_EIG = 2 };
 
@@ -158,6 +159,15 @@ struct dwh_ctx {
   // chunks x frequencies), released with them
   int64_t op_npart = 0;
   double* d_op_part = nullptr;
+  // Nambu cross response (dwh_measure_nambu_response): shares d_rs_ws (W U of
+  // one group of vertices), d_rs_part (the Matsubara pair sums), d_rs_out and
+  // the CSR buffers; d_nb_x keeps X^k = U^H W_k U of every vertex of the call
+  // (a pair needs both of its matrices), d_nb_part the chi2 partials of one
+  // batch of pairs, d_nb_pairs the pair list; released with the above
+  int64_t nb_nx = 0, nb_npart = 0, nb_npairs = 0;
+  double2* d_nb_x = nullptr;
+  double* d_nb_part = nullptr;
+  int* d_nb_pairs = nullptr;
   // own eigensolver (dwhmc_eig.hip) workspace for eig_slots matrices: hemv
   // partials, v ping-pong, w, tridiagonal (d, e), tau, compact-WY T blocks and
   // the back-transform's two nb x n products; the n x n work lives in the

@@ -386,6 +386,23 @@ void launch_op_spec(const double2* Vnm, int64_t sV, int N, const double* E, cons
                     double beta, double eta, double w_start, double w_step, int nw, int nops, double* part,
                     double* out, hipStream_t s);
 
+// Cross response of general Nambu vertices (dwhmc_nambu.hip), one state at a
+// time: X^k = U^H W_k U at X + k sX for every vertex of the call, pairs as 2
+// ints (a_p, b_p) per pair on the device.
+// Pairs per group of the chi2 kernel (one reciprocal serves a group; the last,
+// partial group runs on the instantiation of its own size)
+constexpr int kNbSpecGroup = 4;
+// part[((p nl + l) 2 + c) n2 + m] = Σ_n Re / Im of (r_nm(l) + i s_nm(l)) X^a_nm conj(X^b_nm),
+// p < npairs, l < nl: launch_rs_sum over n2 then gives chi[l + nl p] as (re, im)
+void launch_nb_pairs(const double2* X, int64_t sX, int N, const int* pairs, int npairs, const double* E,
+                     const double* f, const double* g, double beta, int nl, double* part, hipStream_t s);
+// out[2 (j + nw p) + c] = (η/N) Σ_{n,m} (f_n - f_m) Re / Im X^a_nm conj(X^b_nm) / ((ω_j - (E_m - E_n))² + η²)
+// for the pairs p0 <= p < p0 + npairs (out: the call's whole chi2); part:
+// npairs x 2 x op_spec_chunks(N) x nw
+void launch_nb_spec(const double2* X, int64_t sX, int N, const int* pairs, int p0, int npairs, const double* E,
+                    const double* f, const double* g, double beta, double eta, double w_start, double w_step, int nw,
+                    double* part, double* out, hipStream_t s);
+
 // Eigendecomposition leapfrog step (algo eig; U, JU, rho: nc chains of n2 x n2
 // column-major, E: nc x n2): JU = U diag(logistic(-β E)); after rho = JU U^H,
 // P at the bonds, Tr ρ_hh and E_f per chain

@@ -39,15 +39,19 @@ int64_t julia_range_len(double start, double step, double stop) {
 // The current-response workspace (response_run allocates it on first use)
 // goes where the slot buffers are reallocated: both scale with n2², so a
 // caller that grows the slots gets this memory back first.  The operator
-// response (operator_run) works in the same buffers plus its χ'' partials.
+// response (operator_run) works in the same buffers plus its χ'' partials, the
+// Nambu cross response (nambu_run) in them plus its resident X, chi2
+// partials and pair list.
 void response_release(dwh_ctx* ctx) {
   for (void* q : {(void*)ctx->d_rs_ws, (void*)ctx->d_rs_val, (void*)ctx->d_rs_part, (void*)ctx->d_rs_out,
-                  (void*)ctx->d_rs_col, (void*)ctx->d_rs_idx, (void*)ctx->d_op_part})
+                  (void*)ctx->d_rs_col, (void*)ctx->d_rs_idx, (void*)ctx->d_op_part, (void*)ctx->d_nb_x,
+                  (void*)ctx->d_nb_part, (void*)ctx->d_nb_pairs})
     drop_alloc(ctx, q);
-  ctx->d_rs_ws = ctx->d_rs_val = nullptr;
-  ctx->d_rs_part = ctx->d_rs_out = ctx->d_op_part = nullptr;
-  ctx->d_rs_col = ctx->d_rs_idx = nullptr;
+  ctx->d_rs_ws = ctx->d_rs_val = ctx->d_nb_x = nullptr;
+  ctx->d_rs_part = ctx->d_rs_out = ctx->d_op_part = ctx->d_nb_part = nullptr;
+  ctx->d_rs_col = ctx->d_rs_idx = ctx->d_nb_pairs = nullptr;
   ctx->rs_mats = ctx->rs_npart = ctx->rs_nout = ctx->rs_nval = ctx->rs_ncol = ctx->rs_nidx = ctx->op_npart = 0;
+  ctx->nb_nx = ctx->nb_npart = ctx->nb_npairs = 0;
 }
 
 }  // namespace
@@ -1262,6 +1266,148 @@ int operator_run(dwh_ctx* ctx, const TrSrc& src, int m, const OpNambu& op, int64
   return DWH_OK;
 }
 
+// ---------------------------------------------------------------------------
+// cross response of general Nambu vertices (include/dwhmc.h, dwhmc_nambu.hip)
+// ---------------------------------------------------------------------------
+
+// Cap of the resident X^k = U^H W_k U of one call (16 vertices at L = 32)
+constexpr int64_t kNbCapBytes = 1ll << 30;
+// most pairs of a call (blockIdx.y of k_nb_pairs)
+constexpr int64_t kNbMaxPairs = 65535;
+// pairs per chi2 launch: bounds the partials (pairs x 2 x column chunks x n_w doubles)
+constexpr int kNbPairBatch = 4 * dwh::kNbSpecGroup;
+
+// validates the caller's 2N-row CSR and pair list and builds the vertices as
+// build_operator_nambu does (one pattern, duplicates summed, columns ascending
+// inside a row); ctx may be NULL
+int build_nambu_vertices(dwh_ctx* ctx, int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col,
+                         int64_t nnz, const dwh_c128* val, int64_t npairs, const int64_t* pairs, OpNambu* op) {
+  if (N < 1 || N > (1 << 24)) return fail(ctx, DWH_ERR_ARG, "nambu: N must be in [1, 2^24]");
+  if (nops < 1 || nnz < 1) return fail(ctx, DWH_ERR_ARG, "nambu: nops and nnz must be >= 1");
+  if (nops > (1 << 16) || nnz > (1 << 28) || nops * nnz > (1ll << 29))
+    return fail(ctx, DWH_ERR_ARG, "nambu: more than 2^16 vertices or 2^28 entries (2^29 values)");
+  if (npairs < 1 || npairs > kNbMaxPairs) return fail(ctx, DWH_ERR_ARG, "nambu: npairs must be in [1, 65535]");
+  if (!rowptr || !col || !val || !pairs)
+    return fail(ctx, DWH_ERR_ARG, "NULL argument (rowptr, col, val or pairs)");
+  const int64_t n2 = 2 * N;
+  if (rowptr[0] != 0 || rowptr[n2] != nnz)
+    return fail(ctx, DWH_ERR_ARG, "nambu: rowptr must start at 0 and end at nnz");
+  for (int64_t r = 0; r < n2; ++r)
+    if (rowptr[r + 1] < rowptr[r]) return fail(ctx, DWH_ERR_ARG, "nambu: rowptr decreases at row " + std::to_string(r));
+  for (int64_t e = 0; e < nnz; ++e)
+    if (col[e] < 0 || col[e] >= n2)
+      return fail(ctx, DWH_ERR_ARG, "nambu: column " + std::to_string(col[e]) + " outside [0, 2N)");
+  for (int64_t k = 0; k < 2 * npairs; ++k)
+    if (pairs[k] < 0 || pairs[k] >= nops)
+      return fail(ctx, DWH_ERR_ARG, "nambu: pair index " + std::to_string(pairs[k]) + " outside [0, nops)");
+  if ((double)nops * (double)n2 * (double)n2 * 16.0 > (double)kNbCapBytes)
+    return fail(ctx, DWH_ERR_ARG, "nambu: " + std::to_string(nops) + " resident 2N x 2N matrices exceed 1 GiB");
+  std::vector<std::map<int, int>> rows((size_t)n2);
+  for (int64_t r = 0; r < n2; ++r)
+    for (int64_t e = rowptr[r]; e < rowptr[r + 1]; ++e) rows[r][(int)col[e]] = 0;
+  op->rowptr.assign((size_t)n2 + 1, 0);
+  op->col.clear();
+  for (int64_t r = 0; r < n2; ++r) {
+    for (auto& kv : rows[r]) {
+      kv.second = (int)op->col.size();
+      op->col.push_back(kv.first);
+    }
+    op->rowptr[r + 1] = (int)op->col.size();
+  }
+  const int nz = op->nz = (int)op->col.size();
+  op->val.assign((size_t)nops * nz, make_double2(0.0, 0.0));
+  for (int64_t k = 0; k < nops; ++k) {
+    const dwh_c128* v = val + (size_t)k * nnz;
+    double2* o = op->val.data() + (size_t)k * nz;
+    for (int64_t r = 0; r < n2; ++r)
+      for (int64_t e = rowptr[r]; e < rowptr[r + 1]; ++e) {
+        double2& p = o[rows[r][(int)col[e]]];
+        p.x += v[e].re;
+        p.y += v[e].im;
+      }
+  }
+  return DWH_OK;
+}
+
+// the call's workspace (capacities in elements), its vertices and pairs on the
+// device: the buffers of the operator response (W U of one group only), the
+// resident X, the chi2 partials of one batch of pairs and the pair list
+int nambu_prepare(dwh_ctx* ctx, const OpNambu& op, int64_t nops, const std::vector<int>& pairs, int64_t nl,
+                  int64_t nw) {
+  const int64_t n2 = 2 * (int64_t)ctx->d.N, g = rs_group(ctx, nops), np = (int64_t)pairs.size() / 2;
+  const int64_t nb = std::min<int64_t>(np, kNbPairBatch);
+  int rc;
+  if ((rc = rs_grow(ctx, &ctx->d_rs_ws, &ctx->rs_mats, g * n2 * n2)) ||
+      (rc = rs_grow(ctx, &ctx->d_nb_x, &ctx->nb_nx, nops * n2 * n2)) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_part, &ctx->rs_npart, 2 * np * nl * n2)) ||
+      (rc = rs_grow(ctx, &ctx->d_nb_part, &ctx->nb_npart, 2 * nb * dwh::op_spec_chunks(ctx->d.N) * nw)) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_out, &ctx->rs_nout, 2 * np * (nl + nw))) ||
+      (rc = rs_grow(ctx, &ctx->d_nb_pairs, &ctx->nb_npairs, 2 * np)) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_val, &ctx->rs_nval, (int64_t)op.val.size())) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_col, &ctx->rs_ncol, (int64_t)op.col.size())) ||
+      (rc = rs_grow(ctx, &ctx->d_rs_idx, &ctx->rs_nidx, (int64_t)op.rowptr.size())))
+    return rc;
+  hipStream_t s = ctx->stream;
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_rs_val, op.val.data(), op.val.size() * sizeof(double2), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_rs_col, op.col.data(), op.col.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_rs_idx, op.rowptr.data(), op.rowptr.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipMemcpyAsync(ctx->d_nb_pairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHECK(ctx, hipStreamSynchronize(s));
+  return DWH_OK;
+}
+
+// chi[p, l] and chi2[p, j] of the pairs at the m states of src: one batched
+// eigensolve, then per state f_n, U^H once (the slot's Jmn) and per group of
+// vertices W U and the batched product into the resident X; the Matsubara
+// pair sums of all pairs with their fixed-order reduction, and the chi2
+// kernels per batch of pairs.  chi: nl x npairs, chi2: nw x npairs complex per
+// state (host).
+int nambu_run(dwh_ctx* ctx, const TrSrc& src, int m, const OpNambu& op, int64_t nops, const std::vector<int>& pairs,
+              int64_t nl, double eta, double w_start, double w_step, int64_t nw, dwh_c128* chi, dwh_c128* chi2) {
+  int rc;
+  if ((rc = transport_prepare(ctx, std::max<int64_t>(ctx->tr_nw, 0), std::max<int64_t>(ctx->tr_nd, 0), m)))
+    return rc;
+  if ((rc = nambu_prepare(ctx, op, nops, pairs, nl, nw))) return rc;   // (transport_prepare may have released it)
+  if ((rc = eigen_solve(ctx, src, m))) return rc;
+  const int N = ctx->d.N, n2 = 2 * N, np = (int)(pairs.size() / 2);
+  const int64_t sA = (int64_t)n2 * n2, nout = 2 * (int64_t)np * (nl + nw);
+  const int g = rs_group(ctx, nops);
+  hipStream_t s = ctx->stream;
+  double2 *WU = ctx->d_rs_ws, *X = ctx->d_nb_x;
+  double *d_chi = ctx->d_rs_out, *d_chi2 = ctx->d_rs_out + 2 * np * nl;
+  const double2 one = make_double2(1.0, 0.0), zero = make_double2(0.0, 0.0);
+  std::vector<double> out((size_t)m * nout);
+  for (int k = 0; k < m; ++k) {
+    Scope sc(ctx, T_NAMBU, 8.0 * n2 * (double)n2 * n2 * nops);
+    const dwh::TrBufs b = tr_slot(ctx, k);
+    dwh::launch_op_fermi(b.E, N, ctx->beta, b.f, b.g, s);
+    dwh::launch_tr_conj_transpose(b.U, n2, n2, n2, 0, b.Jmn, n2, 0, 1, s);
+    for (int64_t k0 = 0; k0 < nops; k0 += g) {
+      const int gk = (int)std::min<int64_t>(g, nops - k0);
+      dwh::launch_op_apply(b.U, WU, sA, N, ctx->d_rs_idx, ctx->d_rs_col, ctx->d_rs_val + k0 * op.nz, op.nz, gk, s);
+      dwh::gemm_z('N', 'N', n2, n2, n2, one, b.Jmn, n2, 0, WU, n2, sA, zero, X + k0 * sA, n2, sA, gk, s);
+    }
+    if (nl > 0) {
+      dwh::launch_nb_pairs(X, sA, N, ctx->d_nb_pairs, np, b.E, b.f, b.g, ctx->beta, (int)nl, ctx->d_rs_part, s);
+      dwh::launch_rs_sum(ctx->d_rs_part, n2, 2 * np * (int)nl, 1.0 / N, d_chi, s);
+    }
+    if (nw > 0)
+      for (int p0 = 0; p0 < np; p0 += kNbPairBatch)
+        dwh::launch_nb_spec(X, sA, N, ctx->d_nb_pairs, p0, std::min(kNbPairBatch, np - p0), b.E, b.f, b.g, ctx->beta,
+                            eta, w_start, w_step, (int)nw, ctx->d_nb_part, d_chi2, s);
+    HIPCHECK(ctx, hipGetLastError());
+    HIPCHECK(ctx, hipMemcpyAsync(out.data() + (size_t)k * nout, ctx->d_rs_out, nout * sizeof(double),
+                                 hipMemcpyDeviceToHost, s));
+  }
+  if ((rc = eigen_info_check(ctx, m))) return rc;   // (synchronises)
+  for (int k = 0; k < m; ++k) {
+    const dwh_c128* o = reinterpret_cast<const dwh_c128*>(out.data() + (size_t)k * nout);
+    if (nl > 0) std::copy(o, o + np * nl, chi + (size_t)k * np * nl);
+    if (nw > 0) std::copy(o + np * nl, o + np * (nl + nw), chi2 + (size_t)k * np * nw);
+  }
+  return DWH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1561,6 +1707,56 @@ int dwh_debug_operator_nambu(int64_t N, int64_t nops, const int64_t* rowptr, con
   if (!out) return fail(nullptr, DWH_ERR_ARG, "NULL argument (out)");
   OpNambu op;
   if (int rc = build_operator_nambu(nullptr, N, nops, rowptr, col, nnz, val, spin_sign, &op)) return rc;
+  const size_t n2 = 2 * (size_t)N;
+  std::fill(out, out + (size_t)nops * n2 * n2, dwh_c128{0.0, 0.0});
+  for (int64_t k = 0; k < nops; ++k)
+    for (size_t r = 0; r < n2; ++r)
+      for (int e = op.rowptr[r]; e < op.rowptr[r + 1]; ++e) {
+        const double2 v = op.val[(size_t)k * op.nz + e];
+        out[(size_t)k * n2 * n2 + r + (size_t)op.col[e] * n2] = dwh_c128{v.x, v.y};
+      }
+  return DWH_OK;
+}
+
+int dwh_measure_nambu_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta, int64_t nops,
+                               const int64_t* rowptr, const int64_t* col, int64_t nnz, const dwh_c128* val,
+                               int64_t npairs, const int64_t* pairs, int64_t n_matsubara, dwh_c128* chi, double eta,
+                               double w_start, double w_step, int64_t n_w, dwh_c128* chi2) {
+  if (!ctx) return fail(nullptr, DWH_ERR_ARG, "NULL context");
+  if (chain < 0 || chain >= ctx->d.nc) return fail(ctx, DWH_ERR_ARG, "chain index out of range");
+  if (nstates < 1) return fail(ctx, DWH_ERR_ARG, "nstates must be >= 1");
+  if (!Delta && nstates != 1) return fail(ctx, DWH_ERR_ARG, "nstates must be 1 at the device Delta (Delta == NULL)");
+  int rc;
+  OpNambu op;
+  // (the vertex and pair checks first: they bound npairs for the count checks)
+  if ((rc = build_nambu_vertices(ctx, ctx->d.N, nops, rowptr, col, nnz, val, npairs, pairs, &op))) return rc;
+  if ((rc = operator_args(ctx, npairs, n_matsubara, reinterpret_cast<const double*>(chi), eta, w_start, w_step, n_w,
+                          reinterpret_cast<const double*>(chi2))))
+    return rc;
+  std::vector<int> pr(pairs, pairs + 2 * npairs);
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  SETTLE(ctx);
+  if (!Delta)
+    return nambu_run(ctx, chains_src(ctx, chain), 1, op, nops, pr, n_matsubara, eta, w_start, w_step, n_w, chi, chi2);
+  if ((rc = stage_deltas(ctx, nstates, Delta))) return rc;
+  const int64_t n2 = 2 * (int64_t)ctx->d.N;
+  const int group = tr_group(ctx, nstates);   // as dwh_measure_transport_deltas
+  for (int64_t s0 = 0; s0 < nstates; s0 += group) {
+    const int m = (int)std::min<int64_t>(group, nstates - s0);
+    const TrSrc src{ctx->d_tr_stage + s0 * n2, n2, chain, 0};
+    if ((rc = nambu_run(ctx, src, m, op, nops, pr, n_matsubara, eta, w_start, w_step, n_w,
+                        chi ? chi + (size_t)s0 * npairs * n_matsubara : nullptr,
+                        chi2 ? chi2 + (size_t)s0 * npairs * n_w : nullptr)))
+      return rc;
+  }
+  return DWH_OK;
+}
+
+int dwh_debug_nambu_dense(int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
+                          const dwh_c128* val, int64_t npairs, const int64_t* pairs, dwh_c128* out) {
+  if (!out) return fail(nullptr, DWH_ERR_ARG, "NULL argument (out)");
+  OpNambu op;
+  if (int rc = build_nambu_vertices(nullptr, N, nops, rowptr, col, nnz, val, npairs, pairs, &op)) return rc;
   const size_t n2 = 2 * (size_t)N;
   std::fill(out, out + (size_t)nops * n2 * n2, dwh_c128{0.0, 0.0});
   for (int64_t k = 0; k < nops; ++k)

@@ -162,6 +162,66 @@ def operator_csv_line(sweep: int, chi) -> str:
     return ",".join(["%d" % sweep] + ["%.12e" % v for v in np.asarray(chi).ravel()]) + "\n"
 
 
+class _NambuOpts(dict):
+    """a `nambu_response` option after _nambu_opts parsed it"""
+
+
+def _nambu_opts(nambu_response: dict, p) -> dict:
+    """vertices / pairs / n_matsubara / omega / eta of a run's `nambu_response`
+    option: the vertices built once (vertices.build_nambu), pairs defaulting to
+    every (k, k), the grid as (start, step, count) or None, eta defaulting to
+    the run's.  Options parsed before (the drivers hand theirs to their
+    TransportQueues) are returned as they are."""
+    if isinstance(nambu_response, _NambuOpts):
+        return nambu_response
+    extra = set(nambu_response) - {"vertices", "pairs", "n_matsubara", "omega", "eta"}
+    if extra:
+        raise ValueError(f"nambu_response: unknown keys {sorted(extra)}")
+    names = [(str(kind), (int(m[0]), int(m[1])))
+             for kind, m in nambu_response.get("vertices", [("pair_d_create", (0, 0))])]
+    if not names:
+        raise ValueError("nambu_response: vertices is empty")
+    verts = [VX.build_nambu(kind, p, mx, my) for kind, (mx, my) in names]
+    pairs = nambu_response.get("pairs")
+    pairs = [(k, k) for k in range(len(names))] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+    if not pairs or any(not (0 <= a < len(names) and 0 <= b < len(names)) for a, b in pairs):
+        raise ValueError("nambu_response: pairs must be a non-empty list of vertex index pairs")
+    omega = nambu_response.get("omega")
+    if omega is not None:
+        if set(omega) != {"start", "step", "count"}:
+            raise ValueError("nambu_response: omega needs exactly start, step and count")
+        omega = (float(omega["start"]), float(omega["step"]), int(omega["count"]))
+    nl = int(nambu_response.get("n_matsubara", 1))
+    if nl < 0 or (nl == 0 and omega is None):
+        raise ValueError("nambu_response: n_matsubara >= 0, and an omega grid when it is 0")
+    return _NambuOpts(names=names, vertices=verts, pairs=pairs, n_matsubara=nl, omega=omega,
+                      eta=float(nambu_response.get("eta", p.eta)))
+
+
+def nambu_csv_header(opts: dict) -> str:
+    """sweep, then re and im of chi pair by pair, l fastest, named by the pair's
+    two vertices (kind and momentum) and l."""
+    def nm(k):
+        kind, (mx, my) = opts["names"][k]
+        return f"{kind}[mx={mx};my={my}]"
+    return ",".join(["sweep"] + [f"{part}_chi({nm(a)}|{nm(b)};l={l})" for a, b in opts["pairs"]
+                                 for l in range(opts["n_matsubara"]) for part in ("re", "im")])
+
+
+def nambu_csv_line(sweep: int, chi) -> str:
+    c = np.asarray(chi, dtype=np.complex128).ravel()
+    return ",".join(["%d" % sweep] + ["%.12e" % v for z in c for v in (z.real, z.imag)]) + "\n"
+
+
+def write_nambu_header(spec_dir: str, opts: dict) -> None:
+    """nambu_chi2_omega.npy: the chi2 grid of the nambu_response option."""
+    if opts["omega"] is None:
+        return
+    os.makedirs(spec_dir, exist_ok=True)
+    w0, dw, nw = opts["omega"]
+    np.save(os.path.join(spec_dir, "nambu_chi2_omega.npy"), w0 + dw * np.arange(nw))
+
+
 def write_chi2_header(spec_dir: str, opts: dict) -> None:
     """chi2_omega.npy: the χ'' grid of the operator_response option."""
     if opts["omega"] is None:
@@ -176,7 +236,8 @@ class SpectraBins:
     bin_size measurements, then writes their mean as group sweep_<i>.  With
     spectral maps (add's `maps`: the ldos / akw of that measurement, each
     (count, Ly, Lx)) the group also holds their bin means, summed the same way;
-    so it does for chi2 ((nops, n_w)) of the operator_response option."""
+    so it does for chi2 ((nops, n_w)) of the operator_response option and the
+    complex nambu_chi2 ((npairs, n_w)) of the nambu_response option."""
 
     def __init__(self):
         self.count = 0
@@ -187,7 +248,8 @@ class SpectraBins:
         arrs = [spec.optical_conductivity, spec.dos, spec.dos_AN, spec.A_k_omega0]
         if self.count == 0:
             self.acc = [np.array(a, dtype=np.float64, copy=True) for a in arrs]
-            self.maps = None if maps is None else {k: np.array(v, dtype=np.float64, copy=True)
+            # (float64 for every real map, as before; nambu_chi2 is complex and stays so)
+            self.maps = None if maps is None else {k: np.array(v, dtype=np.result_type(v, np.float64), copy=True)
                                                    for k, v in maps.items()}
         else:
             for a, b in zip(self.acc, arrs):
@@ -227,6 +289,7 @@ class ChainOutput:
         self.out_dir = out_dir
         self.f_resp = None           # current_response.csv, only with the current_response option
         self.f_oper = None           # operator_response.csv, only with the operator_response option
+        self.f_nambu = None          # nambu_response.csv, only with the nambu_response option
 
     def tee(self, msg: str):
         line = f"[{datetime.now().strftime('%Y-%m-%d %H:%M:%S')}] {msg}"
@@ -269,6 +332,16 @@ class ChainOutput:
         self.f_oper.write(operator_csv_line(i, chi))
         self.f_oper.flush()
 
+    def nambu(self, i, opts, chi):
+        """One row of nambu_response.csv (created, with its header, by the first)."""
+        if opts["n_matsubara"] < 1:
+            return
+        if self.f_nambu is None:
+            self.f_nambu = open(os.path.join(self.out_dir, "nambu_response.csv"), "w")
+            self.f_nambu.write(nambu_csv_header(opts) + "\n")
+        self.f_nambu.write(nambu_csv_line(i, chi))
+        self.f_nambu.flush()
+
     def close(self):
         self.f_log.close()
         self.f_obs.close()
@@ -277,6 +350,8 @@ class ChainOutput:
             self.f_resp.close()
         if self.f_oper is not None:
             self.f_oper.close()
+        if self.f_nambu is not None:
+            self.f_nambu.close()
 
 
 def thermalize(cache, p, state, out: ChainOutput, n_therm: int, Nt_therm_init: int, rng):
@@ -318,16 +393,21 @@ class TransportQueue:
     (measure_current_response, batched the same way).  operator_response
     (ops / n_matsubara / omega / eta, or None): every measurement also
     appends its row (sweep, χ) to operator_response.csv and puts χ''(ω) into
-    the bins as chi2 (measure_operator_response, batched the same way)."""
+    the bins as chi2 (measure_operator_response, batched the same way).
+    nambu_response (vertices / pairs / n_matsubara / omega / eta, or None):
+    every measurement also appends its row (sweep, re and im of chi) to
+    nambu_response.csv and puts the complex chi2 into the bins as nambu_chi2
+    (measure_nambu_response, batched the same way)."""
 
     def __init__(self, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int, chain: int = 0,
                  spectral_maps: dict | None = None, current_response: dict | None = None,
-                 operator_response: dict | None = None):
+                 operator_response: dict | None = None, nambu_response: dict | None = None):
         self.ctx, self.p, self.out, self.res = ctx, p, out, res
         self.bin_size, self.batch, self.chain = bin_size, max(1, int(batch)), chain
         self.window = None if spectral_maps is None else _maps_window(spectral_maps)
         self.response = None if current_response is None else _response_opts(current_response)
         self.operator = None if operator_response is None else _operator_opts(operator_response, p)
+        self.nambu = None if nambu_response is None else _nambu_opts(nambu_response, p)
         self.pending = []            # (sweep, Δ snapshot)
 
     def add(self, sweep: int, Delta):
@@ -359,17 +439,25 @@ class TransportQueue:
         if self.operator is not None:
             deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
             oper = measure_operator_option(self.ctx, self.operator, self.chain, deltas)
+        nam = None
+        if self.nambu is not None:
+            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
+            nam = measure_nambu_option(self.ctx, self.nambu, self.chain, deltas)
         for k, ((i, _), r) in enumerate(zip(self.pending, specs)):
             spec = H.SpectrumResult(**r)
             extra = None if maps is None else {"ldos": maps["ldos"][k], "akw": maps["akw"][k]}
             if oper is not None and self.operator["omega"] is not None:
                 extra = dict(extra or {}, chi2=oper["chi2"][k])
+            if nam is not None and self.nambu["omega"] is not None:
+                extra = dict(extra or {}, nambu_chi2=nam["chi2"][k])
             self.out.transport(i, spec, self.bin_size, extra)
             self.res.transport.append((i, spec))
             if resp is not None:
                 self.out.response(i, self.response, float(resp["dia"][k]), resp["lam"][k])
             if oper is not None:
                 self.out.operator(i, self.operator, oper["chi"][k])
+            if nam is not None:
+                self.out.nambu(i, self.nambu, nam["chi"][k])
         self.pending = []
 
 
@@ -384,13 +472,25 @@ def measure_operator_option(ctx, opts: dict, chain: int, deltas) -> dict:
     return r
 
 
+def measure_nambu_option(ctx, opts: dict, chain: int, deltas) -> dict:
+    """measure_nambu_response for the nambu_response option: complex chi
+    (nstates, npairs, n_matsubara) and chi2 (nstates, npairs, n_w), one state
+    at the device Δ when deltas is None."""
+    r = ctx.measure_nambu_response(opts["vertices"], opts["pairs"], n_matsubara=opts["n_matsubara"],
+                                   omega=opts["omega"], eta=opts["eta"], chain=chain, deltas=deltas)
+    if deltas is None:
+        return dict(chi=r["chi"][None], chi2=r["chi2"][None])
+    return r
+
+
 def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_measure: int = 500,
                    Nt_therm_init: int = 10, Nt_measure: int = 5, measure_transport_freq: int = 1,
                    bin_size: int = 5, verbose: bool = True, rng: np.random.Generator | None = None,
                    device: int = 0, delta_cap: float = 0.0, state: H.SimulationState | None = None,
                    cache: H.ComputeCache | None = None, transport_batch: int = 1,
                    spectral_maps: dict | None = None, current_response: dict | None = None,
-                   operator_response: dict | None = None) -> SimulationResult:
+                   operator_response: dict | None = None,
+                   nambu_response: dict | None = None) -> SimulationResult:
     """src/Simulation.jl:34-236.  Files in out_dir: simulation.log (appended),
     observables.csv, transport.csv (one row per transport measurement, every
     measure_transport_freq sweeps; <= 0 disables), and spectra_bins/ — the
@@ -419,11 +519,22 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
     momentum and l, and with an omega grid each sweep_<i>.npz gains the bin
     mean chi2 ((nops, count)) with the grid in spectra_bins/chi2_omega.npy
     (eta defaults to the run's).  None (the default): no such files,
+    everything else as without the option.
+    nambu_response = dict(vertices=[(kind, (mx, my)), ...], pairs=[(a, b), ...],
+    n_matsubara=, omega=dict(start=, step=, count=), eta=) (each optional; kind
+    a key of vertices.NAMBU_KINDS, pairs indices into vertices, default every
+    (k, k); FermionContext.measure_nambu_response): every transport
+    measurement also appends one row (sweep, then re and im of chi pair by
+    pair, l fastest) to nambu_response.csv, whose header names each pair's
+    vertices and l, and with an omega grid each sweep_<i>.npz gains the complex
+    bin mean nambu_chi2 ((npairs, count)) with the grid in
+    spectra_bins/nambu_chi2_omega.npy.  None (the default): no such files,
     everything else as without the option."""
     rng = rng if rng is not None else np.random.default_rng()
     if current_response is not None:
         _response_opts(current_response)
     oper_opts = None if operator_response is None else _operator_opts(operator_response, p)
+    nambu_opts = None if nambu_response is None else _nambu_opts(nambu_response, p)
     out = ChainOutput(out_dir, verbose)
     try:
         out.header(p, n_therm, n_measure, measure_transport_freq, bin_size)
@@ -440,6 +551,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
                 write_maps_header(out.spec_dir, p, spectral_maps)
             if oper_opts is not None:
                 write_chi2_header(out.spec_dir, oper_opts)
+            if nambu_opts is not None:
+                write_nambu_header(out.spec_dir, nambu_opts)
         Nt_fin, acc_th = thermalize(cache, p, state, out, n_therm, Nt_therm_init, rng)
 
         dt_meas = H.calc_optimal_dt(p.beta, p.J, p.mass, Nt_measure)
@@ -449,7 +562,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         acc_total = 0
         res = SimulationResult(Nt_fin, acc_th, 0.0)
         tq = TransportQueue(cache.require(), p, out, res, bin_size, transport_batch, spectral_maps=spectral_maps,
-                            current_response=current_response, operator_response=operator_response)
+                            current_response=current_response, operator_response=operator_response,
+                            nambu_response=nambu_opts)
         for i in range(1, n_measure + 1):
             acc, dH = H.hmc_sweep(cache, p, state, Nt=Nt_measure, dt=dt_meas, rng=rng)
             acc_total += int(acc)
@@ -473,7 +587,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                           bin_size: int = 5, verbose: bool = False, device: int = 0,
                           delta_cap: float = 0.0, transport_batch: int = 1,
                           spectral_maps: dict | None = None, current_response: dict | None = None,
-                          operator_response: dict | None = None) -> list:
+                          operator_response: dict | None = None,
+                          nambu_response: dict | None = None) -> list:
     """len(out_dirs) independent run_simulation's (src/Simulation.jl:34-236),
     chain k writing out_dirs[k] and drawing from rngs[k] in the reference's
     order (initialize_state, then per sweep randn(ComplexF64) and rand() only
@@ -489,12 +604,13 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
     backend: on the device the batched context selects one pole set for the
     largest spectral bound over the chains, and a guard trip re-selects it
     for every chain, so dH differs at ~1e-12 and a Metropolis decision can
-    differ).  spectral_maps, current_response, operator_response: as
-    run_simulation's, for every chain."""
+    differ).  spectral_maps, current_response, operator_response,
+    nambu_response: as run_simulation's, for every chain."""
     K = len(out_dirs)
     window = None if spectral_maps is None else _maps_window(spectral_maps)
     response = None if current_response is None else _response_opts(current_response)
     oper_opts = None if operator_response is None else _operator_opts(operator_response, p)
+    nambu_opts = None if nambu_response is None else _nambu_opts(nambu_response, p)
     if len(rngs) != K or K < 1:
         raise ValueError("one rng per output directory")
     outs = [ChainOutput(d, verbose) for d in out_dirs]
@@ -513,6 +629,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                     write_maps_header(outs[k].spec_dir, p, spectral_maps)
                 if oper_opts is not None:
                     write_chi2_header(outs[k].spec_dir, oper_opts)
+                if nambu_opts is not None:
+                    write_nambu_header(outs[k].spec_dir, nambu_opts)
             Nt_fin, acc_th = thermalize(cache, p, st, outs[k], n_therm, Nt_therm_init, rngs[k])
             cache.ctx.close()
             states.append(st)
@@ -532,7 +650,7 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
             acc_total = np.zeros(K, dtype=np.int64)
             tqs = [TransportQueue(ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k,
                                   spectral_maps=spectral_maps, current_response=current_response,
-                                  operator_response=operator_response)
+                                  operator_response=operator_response, nambu_response=nambu_opts)
                    for k in range(K)] if transport_batch > 1 else None
             for i in range(1, n_measure + 1):
                 noise = np.stack([H.standard_complex_normal(r, (p.N, 2)) for r in rngs])
@@ -562,6 +680,9 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                         oper = None if oper_opts is None else measure_operator_option(ctx, oper_opts, k, None)
                         if oper is not None and oper_opts["omega"] is not None:
                             maps = dict(maps or {}, chi2=oper["chi2"][0])
+                        nam = None if nambu_opts is None else measure_nambu_option(ctx, nambu_opts, k, None)
+                        if nam is not None and nambu_opts["omega"] is not None:
+                            maps = dict(maps or {}, nambu_chi2=nam["chi2"][0])
                         outs[k].transport(i, spec, bin_size, maps)
                         results[k].transport.append((i, spec))
                         if response is not None:
@@ -569,6 +690,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                             outs[k].response(i, response, r["dia"], r["lam"])
                         if oper is not None:
                             outs[k].operator(i, oper_opts, oper["chi"][0])
+                        if nam is not None:
+                            outs[k].nambu(i, nambu_opts, nam["chi"][0])
                     if i % 10 == 0:
                         outs[k].tee("Meas %d/%d. Acc=%.2f. E=%.4f" % (i, n_measure, acc_total[k] / i,
                                                                      obs.total_energy))

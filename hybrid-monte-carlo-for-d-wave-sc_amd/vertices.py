@@ -16,6 +16,20 @@ phase φ_b(i) = exp(-i q·(r_i + δ_b/2)) on a bond b from i to j_b(i) = i + δ_
                     b = (+x, g = +1), (+y, g = -1):  γ_k = 2t (cos kx - cos ky), s = +1
     raman_b2g       the same with t' on (+x+y, +1), (+x-y, -1):
                     γ_k = -4t' sin kx sin ky,             s = +1
+
+For FermionContext.measure_nambu_response a vertex is a `NambuVertex`: the
+COO triplets of any complex 2N x 2N matrix W, the operator Ψ† W Ψ in the basis
+Ψ = (c_{i↑}; c†_{i↓}); D = W[:N, N:] multiplies c†_{i↑} c†_{j↓}:
+
+    nambu(vertex, N)     V ⊕ (-s V^T) of a Vertex
+    pair_field           the singlet pair field of a form factor at q:
+                         D[i, j_b] += g_b φ_b(i), D[j_b, i] += g_b φ_b(i)
+                         ("d": (+x, +1), (+y, -1); "s_ext": (+x, +1), (+y, +1);
+                         "s": D[i, i] = e^{-i q·r_i}); part "create":
+                         C = [[0, D], [0, 0]], "destroy": C†, "amplitude":
+                         C + C†, "phase": i (C - C†)
+    hamiltonian          H_BdG(Δ) itself, entry for entry what the device assembles
+    commutator_with_h    i (H W - W H)
 """
 from __future__ import annotations
 
@@ -144,3 +158,187 @@ def union_csr(ops, N: int):
         np.add.at(val[k], np.searchsorted(pat, r * N + c), v)
     rowptr = np.searchsorted(pat // N, np.arange(N + 1)).astype(np.int64)
     return rowptr, (pat % N).astype(np.int64), val
+
+
+# --------------------------------------------------------------------------
+# general Nambu vertices (FermionContext.measure_nambu_response)
+# --------------------------------------------------------------------------
+class NambuVertex(NamedTuple):
+    row: np.ndarray        # int64, in [0, 2N)
+    col: np.ndarray        # int64, in [0, 2N)
+    val: np.ndarray        # complex128
+
+    def dense(self, N: int) -> np.ndarray:
+        W = np.zeros((2 * N, 2 * N), dtype=np.complex128)
+        np.add.at(W, (self.row, self.col), self.val)
+        return W
+
+
+def _nv(rows, cols, vals) -> NambuVertex:
+    return NambuVertex(np.concatenate(rows).astype(np.int64), np.concatenate(cols).astype(np.int64),
+                       np.concatenate(vals).astype(np.complex128))
+
+
+def nambu(vertex: Vertex, N) -> NambuVertex:
+    """V ⊕ (-s V^T): the Nambu matrix of a Vertex on N sites (N, or anything with .N)."""
+    N = int(getattr(N, "N", N))
+    r, c, v = as_triplets(vertex, N)
+    return _nv([r, c + N], [c, r + N], [v, -float(vertex.spin_sign) * v])
+
+
+PAIR_FORMS = {"d": [("+x", 1.0), ("+y", -1.0)], "s_ext": [("+x", 1.0), ("+y", 1.0)], "s": None}
+PAIR_PARTS = ("create", "destroy", "amplitude", "phase")
+
+
+def pair_field(p, mx: int = 0, my: int = 0, form: str = "d", part: str = "create") -> NambuVertex:
+    """The singlet pair field Σ D_ij c†_{i↑} c†_{j↓} (D symmetric) of form
+    factor `form` at q = 2π (mx/Lx, my/Ly), or its adjoint / Hermitian parts."""
+    if form not in PAIR_FORMS:
+        raise ValueError(f"unknown pair form {form!r}; one of {sorted(PAIR_FORMS)}")
+    if part not in PAIR_PARTS:
+        raise ValueError(f"unknown part {part!r}; one of {PAIR_PARTS}")
+    i, _, _ = _sites(p)
+    N = p.N
+    if PAIR_FORMS[form] is None:
+        rows, cols, vals = [i], [i], [_phase(p, mx, my, (0, 0))]
+    else:
+        lists = _bond_lists(p)
+        rows, cols, vals = [], [], []
+        for name, g in PAIR_FORMS[form]:
+            j, d = lists[name]
+            v = g * _phase(p, mx, my, d)
+            rows += [i, j]
+            cols += [j, i]
+            vals += [v, v]
+    r, c, v = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals).astype(np.complex128)
+    cre = (r, c + N, v)                       # C = [[0, D], [0, 0]]
+    des = (c + N, r, np.conj(v))              # C†
+    if part == "create":
+        return _nv(*[[a] for a in cre])
+    if part == "destroy":
+        return _nv(*[[a] for a in des])
+    if part == "amplitude":
+        return _nv([cre[0], des[0]], [cre[1], des[1]], [cre[2], des[2]])
+    return _nv([cre[0], des[0]], [cre[1], des[1]], [1j * cre[2], -1j * des[2]])
+
+
+def hamiltonian(p, disorder, delta) -> NambuVertex:
+    """H_BdG(Δ) as sparse triplets without duplicates: the reference's upper
+    triangle (diagonal w_i - μ, hoppings -t / -t' to the neighbours j > i, the
+    hole block their negatives, pairing Δ[i, 0]/2 at (i, i+x + N) and
+    (i+x, i + N), Δ[i, 1]/2 at +y; later writes overwrite earlier ones, which
+    matters on 1- and 2-site rings) and its Hermitian completion."""
+    N = p.N
+    nn, nnn = np.asarray(p.nn_table) - 1, np.asarray(p.nnn_table) - 1
+    disorder = np.asarray(disorder, dtype=np.float64).ravel()
+    delta = np.asarray(delta, dtype=np.complex128).reshape(N, 2)
+    up = {}
+    for i in range(N):
+        term = disorder[i] - p.mu
+        up[(i, i)] = term
+        up[(i + N, i + N)] = -term
+    for i in range(N):
+        for tab, hop in ((nn, p.t), (nnn, p.tp)):
+            for d in range(4):
+                j = int(tab[i, d])
+                if j > i:
+                    up[(i, j)] = -hop
+                    up[(i + N, j + N)] = hop
+    for i in range(N):
+        for b in range(2):
+            j = int(nn[i, b])
+            v = 0.5 * delta[i, b]
+            up[(i, j + N)] = v
+            up[(j, i + N)] = v
+    rows, cols, vals = [], [], []
+    for (r, c), v in up.items():
+        rows.append(r)
+        cols.append(c)
+        vals.append(v)
+        if r != c:
+            rows.append(c)
+            cols.append(r)
+            vals.append(np.conj(v))
+    return NambuVertex(np.array(rows, dtype=np.int64), np.array(cols, dtype=np.int64),
+                       np.array(vals, dtype=np.complex128))
+
+
+def as_nambu_triplets(op, N: int):
+    """(row, col, val) over 2N of a NambuVertex, a Vertex (lifted by `nambu`),
+    a COO triple or a dense (2N, 2N) matrix."""
+    n2 = 2 * N
+    if isinstance(op, Vertex):
+        op = nambu(op, N)
+    if isinstance(op, NambuVertex):
+        op = (op.row, op.col, op.val)
+    if isinstance(op, (tuple, list)) and len(op) == 3:
+        r, c, v = (np.asarray(a).ravel() for a in op)
+        if not (len(r) == len(c) == len(v)):
+            raise ValueError("COO vertex: row, col and val differ in length")
+        r, c = r.astype(np.int64), c.astype(np.int64)
+        if len(r) and (r.min() < 0 or r.max() >= n2 or c.min() < 0 or c.max() >= n2):
+            raise ValueError(f"COO vertex: index outside [0, {n2})")
+        return r, c, v.astype(np.complex128)
+    W = np.asarray(op, dtype=np.complex128)
+    if W.shape != (n2, n2):
+        raise ValueError(f"expected a NambuVertex, a Vertex, a COO triple or a dense ({n2}, {n2}) matrix")
+    r, c = np.nonzero(W)
+    return r.astype(np.int64), c.astype(np.int64), W[r, c]
+
+
+def _spmm(a, b, n):
+    """COO product a·b of two n x n triplet matrices (duplicates left to add up)."""
+    ar, ac, av = a
+    order = np.argsort(b[0], kind="stable")
+    br, bc, bv = b[0][order], b[1][order], b[2][order]
+    ptr = np.searchsorted(br, np.arange(n + 1))
+    cnt = ptr[ac + 1] - ptr[ac]
+    rep = np.repeat(np.arange(len(ar)), cnt)
+    idx = np.repeat(ptr[ac], cnt) + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    return ar[rep], bc[idx], av[rep] * bv[idx]
+
+
+def commutator_with_h(w, p, disorder, delta) -> NambuVertex:
+    """i (H W - W H) with H = hamiltonian(p, disorder, delta), as a sparse
+    product: the vertex of dO_W/dt at fixed Δ."""
+    n2 = 2 * p.N
+    h = as_nambu_triplets(hamiltonian(p, disorder, delta), p.N)
+    wt = as_nambu_triplets(w, p.N)
+    hw, wh = _spmm(h, wt, n2), _spmm(wt, h, n2)
+    return _nv([hw[0], wh[0]], [hw[1], wh[1]], [1j * hw[2], -1j * wh[2]])
+
+
+def union_csr_nambu(ops, N: int):
+    """union_csr for 2N x 2N vertices: (rowptr (2N+1,), col (nnz,), val (nops, nnz))."""
+    n2 = 2 * N
+    trips = [as_nambu_triplets(op, N) for op in ops]
+    keys = np.concatenate([r * n2 + c for r, c, _ in trips]) if trips else np.zeros(0, dtype=np.int64)
+    pat = np.unique(keys)
+    if len(pat) == 0:
+        pat = np.zeros(1, dtype=np.int64)
+    val = np.zeros((len(trips), len(pat)), dtype=np.complex128)
+    for k, (r, c, v) in enumerate(trips):
+        np.add.at(val[k], np.searchsorted(pat, r * n2 + c), v)
+    rowptr = np.searchsorted(pat // n2, np.arange(n2 + 1)).astype(np.int64)
+    return rowptr, (pat % n2).astype(np.int64), val
+
+
+def _lifted(fn):
+    return lambda p, mx, my: nambu(fn(p, mx, my), p.N)
+
+
+def _pair_kind(form, part):
+    return lambda p, mx, my: pair_field(p, mx, my, form, part)
+
+
+# names for the driver's nambu_response option: every KINDS vertex lifted, and
+# pair_<form>_<part>
+NAMBU_KINDS = {k: _lifted(fn) for k, fn in KINDS.items()}
+NAMBU_KINDS.update({f"pair_{form}_{part}": _pair_kind(form, part) for form in PAIR_FORMS for part in PAIR_PARTS})
+
+
+def build_nambu(kind: str, p, mx: int = 0, my: int = 0) -> NambuVertex:
+    """The Nambu vertex named `kind` (a key of NAMBU_KINDS) at momentum indices (mx, my)."""
+    if kind not in NAMBU_KINDS:
+        raise ValueError(f"unknown Nambu vertex kind {kind!r}; one of {sorted(NAMBU_KINDS)}")
+    return NAMBU_KINDS[kind](p, int(mx), int(my))

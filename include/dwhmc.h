@@ -182,7 +182,7 @@ int dwh_stream(dwh_ctx* ctx, void** stream);
  * (bit 0 "gj_update", bit 1 "gj_pivot", bit 2 "assemble", bit 3 "contract",
  * bit 4 "step", bit 5 "gj_edge", bit 6 "cr_gemm", bit 7 "cr_inv", bit 8 "cr_inv_side",
  * bit 9 "eig_own", bit 10 "eig_vendor", bit 11 "cr_sparse", bit 12 "spectral",
- * bit 13 "response", bit 14 "operator");
+ * bit 13 "response", bit 14 "operator", bit 15 "nambu");
  * 0 disables, -1 times everything. */
 int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
 /* name: "gj_update" (rank-128 paired / rank-64 trailing updates),
@@ -199,7 +199,8 @@ int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
  * its eigensolve, one record per state; work = 8·(2N)³ flops per momentum per
  * state, the J_nm product's), "operator" (the same for
  * dwh_measure_operator_response; work = 8·(2N)³ flops per operator per
- * state), "assemble",
+ * state), "nambu" (the same for dwh_measure_nambu_response; work = 8·(2N)³
+ * flops per vertex per state), "assemble",
  * "contract", "step"; returns total milliseconds, launches and the
  * algorithmic work summed over launches (fp64 flops; HBM bytes for
  * "assemble"). */
@@ -424,6 +425,60 @@ int dwh_measure_operator_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, 
 int dwh_debug_operator_nambu(int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
                              const dwh_c128* val, const int32_t* spin_sign, dwh_c128* out);
 
+/* ---- cross response of general Nambu vertices ------------------------------
+ * The Kubo bubble <O_a ; O_b†> of any two one-body operators, pairing
+ * (anomalous) parts included: pair-field susceptibilities, the amplitude and
+ * phase modes, i[H, ρ_q], Λ_xy, density-current (vertices.py builds these).
+ * The Nambu basis Ψ = (c_{i↑}; d_i = c†_{i↓}), i < N, is not redundant, so
+ * any complex 2N x 2N matrix W is an operator O_W = Ψ† W Ψ (+ a constant):
+ * W[:N, :N] is the particle block, W[N:, N:] the hole block,
+ * D = W[:N, N:] multiplies c†_{i↑} c†_{j↓} and W[N:, :N] multiplies
+ * c_{i↓} c_{j↑}.  With E_n, U the eigenpairs of H_BdG(Δ),
+ * f_n = logistic(-β E_n), ΔE_nm = E_m - E_n, Ω_l = 2π l/β, X^k = U^H W_k U
+ * and, for a pair p = (a, b), M_nm = X^a_nm conj(X^b_nm):
+ *   chi[p, l]  = (1/N) Σ_{n,m<2N} [r_nm(l) + i s_nm(l)] M_nm       (complex)
+ *                r_nm(l) exactly as in dwh_measure_current_response;
+ *                s_nm(0) = 0, s_nm(l >= 1) = (f_n - f_m) Ω_l / (ΔE² + Ω_l²),
+ *                i.e. (f_n - f_m)/(ΔE - iΩ_l)
+ *   chi2[p, j] = (π/N) Σ_{n,m} (f_n - f_m) M_nm L_η(ω_j - ΔE_nm)   (complex)
+ *                over all ordered pairs (n, m), those with |f_n - f_m| < 1e-12
+ *                skipped; ω_j = w_start + j·w_step of either sign.
+ * For a = b and W = V ⊕ (-s V^T), Re chi and chi2 are
+ * dwh_measure_operator_response's χ and χ''.
+ * Vertices: nops matrices on one CSR pattern with 2N rows (0-based, rowptr
+ * 2N + 1 entries, col nnz entries in [0, 2N)), vertex k's values at
+ * val + k·nnz; duplicates are summed, columns inside a row may be unsorted,
+ * the union of several patterns with explicit zeros is fine.  pairs: 2·npairs
+ * indices (a_p, b_p) in [0, nops).  Delta / nstates / chain, skipping a part
+ * with a zero count, every algorithm, one eigensolve per state and "the
+ * context's own Δ is not touched" as in dwh_measure_operator_response.
+ * Outputs:
+ *   chi[l + n_matsubara·(p + npairs·s)],  chi2[j + n_w·(p + npairs·s)].
+ * Per vertex and state one 2N-cubed product on the library's own MFMA kernel
+ * after W U (the sparse kernel of the operator response); X^k stays resident
+ * for all nops vertices (a pair needs both of its matrices), at most 1 GiB
+ * (16 vertices at L = 32): a larger set is DWH_ERR_ARG.  Only the W U scratch
+ * runs in the groups of the current response (DWHMC_RESPONSE_GROUP=g lowers
+ * them).  chi2 takes one reciprocal per (n, m, ω) for a group of 4 pairs and
+ * min(2N, 512)·n_w·2 doubles of partial sums per pair, 16 pairs at a time
+ * (dwhmc_nambu.hip).  Every sum has a fixed order: two calls give the same
+ * bits, a batch of snapshots equals its single-state calls and smaller groups
+ * give the same bits.  Allocated on first use, grown on demand.
+ * DWH_ERR_ARG, nothing launched: every case dwh_measure_operator_response
+ * refuses (the sign aside), a column outside [0, 2N), npairs < 1 or > 65535, a pair
+ * index outside [0, nops), NULL pairs, the resident limit. */
+int dwh_measure_nambu_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta,
+                               int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
+                               const dwh_c128* val, int64_t npairs, const int64_t* pairs,
+                               int64_t n_matsubara, dwh_c128* chi,
+                               double eta, double w_start, double w_step, int64_t n_w, dwh_c128* chi2);
+/* Host only (no device, no context): the validation of the call above and
+ * the CSR it uploads (duplicates summed) expanded to dense: out holds nops
+ * matrices W_k, 2N x 2N column-major.  Errors as above, the text where
+ * dwh_last_error(NULL) reads it. */
+int dwh_debug_nambu_dense(int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
+                          const dwh_c128* val, int64_t npairs, const int64_t* pairs, dwh_c128* out);
+
 /* ---- assembly read-back (parity tests; not on the hot path) -------------
  * The BdG matrix H_BdG(Δ) exactly as the device assembles it, so tests can
  * compare it bit-for-bit with init_static_H! + update_H_BdG!
@@ -453,8 +508,9 @@ int dwh_debug_qeig(dwh_ctx* ctx, int64_t chain, double* E, double* ms);
  * ascending; U is 2N x 2N column-major per state, column n belonging to E[n]
  * (U need not diagonalise anything).  The next eigensolve of this context
  * with exactly nstates matrices — the one dwh_measure_transport(_deltas),
- * dwh_measure_spectral_maps, dwh_measure_current_response and
- * dwh_measure_operator_response run after preparing their buffers — copies
+ * dwh_measure_spectral_maps, dwh_measure_current_response,
+ * dwh_measure_operator_response and dwh_measure_nambu_response run after
+ * preparing their buffers — copies
  * them into its slots instead of solving, reports the solve as particle-hole
  * closed (dwh_info_t::eig_half) iff ph != 0 and as not structure-preserving
  * (eig_quat = 0), and clears the staging: the injection is one-shot.  With

@@ -268,6 +268,38 @@ function measure_operator_response(cache::GPUCache, p::ModelParameters, rowptr::
     return χ, χ2
 end
 
+# The cross response <O_a ; O_b†> of general Nambu vertices O_k = Ψ† W_k Ψ,
+# Ψ = (c_{i↑}; c†_{i↓}), pairing blocks included, for the Δ the context holds
+# (dwh_measure_nambu_response), the CSR form: one pattern with 2N rows for all
+# vertices, 0-based (`rowptr` of 2N + 1 entries, `col` of nnz entries in
+# [0, 2N), duplicates add up), `val[e, k]` the nnz values of vertex k, and
+# `pairs[:, p]` = (a_p, b_p), 0-based vertex indices.  Returns (χ, χ2), both
+# complex: χ[l + 1, p] = (1/N) Σ (f_n - f_m)/(ΔE - iΩ_l) X^a_nm conj(X^b_nm)
+# with the l = 0 rules of measure_current_response, χ2[j + 1, p] on
+# ω_j = ω_start + j·ω_step, j < n_ω.  n_matsubara = 0 or n_ω = 0 skips that
+# part.  Not run; the same ABI call is exercised through ctypes by
+# tests/test_nambu_response.py.
+function measure_nambu_response(cache::GPUCache, p::ModelParameters, rowptr::Vector{Int64},
+                                col::Vector{Int64}, val::Matrix{ComplexF64}, pairs::Matrix{Int64};
+                                n_matsubara::Integer=1, η::Real=p.η, ω_start::Real=0.0, ω_step::Real=0.0,
+                                n_ω::Integer=0)
+    nnz, nops = size(val)
+    length(col) == nnz || throw(ArgumentError("val must be nnz x nops with nnz = length(col)"))
+    length(rowptr) == 2 * p.N + 1 || throw(ArgumentError("rowptr must have 2N + 1 entries"))
+    size(pairs, 1) == 2 || throw(ArgumentError("pairs must be 2 x npairs"))
+    npairs = size(pairs, 2)
+    χ = zeros(ComplexF64, max(n_matsubara, 0), npairs)
+    χ2 = zeros(ComplexF64, max(n_ω, 0), npairs)
+    GC.@preserve rowptr col val pairs χ χ2 check(cache.ctx, ccall((:dwh_measure_nambu_response, libdwhmc), Cint,
+                           (Ptr{Cvoid}, Int64, Int64, Ptr{ComplexF64}, Int64, Ptr{Int64}, Ptr{Int64}, Int64,
+                            Ptr{ComplexF64}, Int64, Ptr{Int64}, Int64, Ptr{ComplexF64}, Float64, Float64, Float64,
+                            Int64, Ptr{ComplexF64}),
+                           cache.ctx, 0, 1, C_NULL, nops, pointer(rowptr), pointer(col), nnz, pointer(val),
+                           npairs, pointer(pairs), n_matsubara, n_matsubara > 0 ? pointer(χ) : C_NULL,
+                           Float64(η), Float64(ω_start), Float64(ω_step), n_ω, n_ω > 0 ? pointer(χ2) : C_NULL))
+    return χ, χ2
+end
+
 # ---------------------------------------------------------------------------
 # run_simulation on the GPU.  The reference constructs its cache inside the
 # driver (`cache = initialize_cache(p)`, src/Simulation.jl:82), so the driver
