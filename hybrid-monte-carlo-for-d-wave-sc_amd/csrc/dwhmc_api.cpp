@@ -137,33 +137,34 @@ void cr_enqueue(dwh_ctx* ctx) {
       Scope s(ctx, T_CR_INVSIDE, st.n * bp3 + st.flops * c.nbatch);
       dwh::launch_cr_inv_side(c, ctx->bpool, ctx->d_inv_blk + st.first, ctx->d_inv_dst + st.first,
                               ctx->d_inv_slot + st.first, st.n, ctx->ldpart, ctx->d_tasks + st.tfirst,
-                              st.ntiles, st.maxt32, ctx->stream, guard);
+                              st.ntiles, st.maxt32, ctx->stream, guard, st.store, st.store_side);
       guard = dwh::SiteGuard{};
     } else if (st.kind == 0 && st.l0) {
       Scope s(ctx, T_CR_INV, st.n * bp3);
       dwh::launch_cr_inv0(c, ctx->bpool, ctx->d_inv_blk + st.first, ctx->d_inv0_r, ctx->d_inv_dst + st.first,
                           ctx->d_inv_slot + st.first, st.n, ctx->ldpart, ctx->ldA, ctx->stream, guard.Delta,
-                          guard.site4, guard.cap4, guard.flag);
+                          guard.site4, guard.cap4, guard.flag, st.store);
       guard = dwh::SiteGuard{};
     } else if (st.kind == 0) {
       Scope s(ctx, T_CR_INV, st.n * bp3);
       dwh::launch_cr_inv(c, ctx->bpool, ctx->d_inv_blk + st.first, ctx->d_inv_dst + st.first,
-                         ctx->d_inv_slot + st.first, st.n, ctx->ldpart, ctx->stream, guard);
+                         ctx->d_inv_slot + st.first, st.n, ctx->ldpart, ctx->stream, guard, st.store);
       guard = dwh::SiteGuard{};
     } else if (st.kind == 2) {
       Scope s(ctx, T_CR_SPARSE, st.flops * c.nbatch);
       const size_t spE = (size_t)dwh::kCrSpNZ * c.BP, HP = (size_t)c.BP / 2;
       if (st.sp == 0)
         dwh::launch_cr_sp_fwd(c, ctx->bpool, ctx->d_sp_rf + st.first * HP, st.n, ctx->d_sp_cv + st.first * 3 * spE,
-                              ctx->d_sp_cm + st.first * 3 * spE, ctx->Delta, ctx->stream);
+                              ctx->d_sp_cm + st.first * 3 * spE, ctx->Delta, ctx->stream, st.store);
       else
         dwh::launch_cr_sp_bwd(c, ctx->bpool, ctx->d_sp_rb + st.first * HP, st.n,
                               ctx->d_sp_cv + ctx->sp_arr.col_bwd0 + st.first * 2 * spE,
-                              ctx->d_sp_cm + ctx->sp_arr.col_bwd0 + st.first * 2 * spE, ctx->Delta, ctx->stream);
+                              ctx->d_sp_cm + ctx->sp_arr.col_bwd0 + st.first * 2 * spE, ctx->Delta, ctx->stream,
+                              st.store);
     } else {
       Scope s(ctx, T_CR_GEMM, st.flops * c.nbatch);
       dwh::launch_cr_gemm(c, ctx->bpool, ctx->d_tasks + st.first, st.n, st.maxt32, st.maxt16,
-                          ctx->d_slots + st.sfirst, st.nswg, st.cfg, st.sg, ctx->stream);
+                          ctx->d_slots + st.sfirst, st.nswg, st.cfg, st.sg, ctx->stream, st.store);
     }
   }
 }
@@ -226,7 +227,7 @@ void factorize_enqueue(dwh_ctx* ctx, const dwh::KickDrift& kd) {
     // the kernel scatters the drifted Δ into the pool only when it drifts
     ctx->pairing_in_pool = kd.drift != 0.0;
     dwh::launch_cr_pair_force(ctx->cr, ctx->bpool, ctx->d_bond4, ctx->d_c, ctx->Delta, ctx->Pair, ctx->F, ctx->Pi,
-                              kd, ctx->beta, ctx->J, ctx->stream);
+                              kd, ctx->beta, ctx->J, ctx->stream, ctx->plan.store_force);
     return;
   }
   dwh::launch_dvals(d, ctx->Dsrc, ctx->Delta, ctx->Dv, ctx->stream);

@@ -245,7 +245,7 @@ __device__ __forceinline__ void mma16_3m_T(d4& cr, d4& ci, const double2* A, con
 
 // one workgroup (NT waves) inverts block blk[li] of batch item bi; pan / ldw:
 // the caller's LDS (double-buffered panel, per-wave ln|det| partials)
-template <int NT>
+template <int NT, int ST = kStorePlain>
 __device__ __forceinline__ void cr_inv_wg(double2* __restrict__ pool, int64_t item, int bi, int li,
                                           const int* __restrict__ blk, const int* __restrict__ dst,
                                           const int* __restrict__ slot, double* __restrict__ ldpart,
@@ -417,7 +417,7 @@ __device__ __forceinline__ void cr_inv_wg(double2* __restrict__ pool, int64_t it
   for (int I = 0; I < NT / 2; ++I)
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr)
-      Mo[(int64_t)(I * 16 + lk + 4 * rr) * BP + w * 16 + lr] = make_double2(ar[I][rr], ai[I][rr]);
+      st16<ST>(Mo + (int64_t)(I * 16 + lk + 4 * rr) * BP + w * 16 + lr, make_double2(ar[I][rr], ai[I][rr]));
   if (l == 0) ldw[w] = 0.5 * log(pp);
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -451,7 +451,7 @@ __device__ __forceinline__ void site_guard_wg(const SiteGuard& sg, int N, int c)
 }
 
 // gcol: the guard column's x (-1: no guard); arguments in first-use order
-template <int NT>
+template <int NT, int ST>
 __global__ __launch_bounds__(64 * NT) void k_cr_inv(double2* __restrict__ pool, int64_t item,
                                                     const int* __restrict__ blk,
                                                     const int* __restrict__ dst, int gcol,
@@ -465,7 +465,7 @@ __global__ __launch_bounds__(64 * NT) void k_cr_inv(double2* __restrict__ pool, 
     if (xy.y % P == 0) site_guard_wg(sg, N, xy.y / P);
     return;
   }
-  cr_inv_wg<NT>(pool, item, xy.y, xy.x, blk, dst, slot, ldpart, nslots, pan, ldw);
+  cr_inv_wg<NT, ST>(pool, item, xy.y, xy.x, blk, dst, slot, ldpart, nslots, pan, ldw);
 }
 
 // ---------------------------------------------------------------------------
@@ -522,6 +522,7 @@ __device__ __forceinline__ void inv0_site_guard(const double2* __restrict__ D, c
 }
 
 // gcol: the guard column's x (-1: no guard); arguments in first-use order
+template <int ST>
 __global__ __launch_bounds__(256) void k_cr_inv0(double2* __restrict__ pool, int64_t item,
                                                  const int* __restrict__ blk, const int* __restrict__ rblk,
                                                  const int* __restrict__ dst, int gcol,
@@ -649,8 +650,8 @@ __global__ __launch_bounds__(256) void k_cr_inv0(double2* __restrict__ pool, int
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
     const int row = ti * 16 + lk + 4 * rr, col = tj * 16 + lr;
-    Mo[(int64_t)row * BP + col] = make_double2(xr[rr], xi[rr]);
-    Mo[(int64_t)row * BP + HP + col] = make_double2(yr[rr], yi[rr]);
+    st16<ST>(Mo + (int64_t)row * BP + col, make_double2(xr[rr], xi[rr]));
+    st16<ST>(Mo + (int64_t)row * BP + HP + col, make_double2(yr[rr], yi[rr]));
   }
   if (l == 0 && (w == 0 || w == 3)) ldw[w == 3] = 0.5 * log(pp);
   __syncthreads();
@@ -674,6 +675,7 @@ __global__ __launch_bounds__(256) void k_cr_inv0(double2* __restrict__ pool, int
 // register inversions on the chain instead of k_cr_inv<6>'s six, and a
 // quarter of its flops.  The R and B tiles' LDS becomes the Gauss-Jordan
 // buffers once S is formed.
+template <int ST>
 __global__ __launch_bounds__(576) void k_cr_inv0_96(double2* __restrict__ pool, int64_t item,
                                                     const int* __restrict__ blk, const int* __restrict__ rblk,
                                                     const int* __restrict__ dst, int gcol,
@@ -763,8 +765,8 @@ __global__ __launch_bounds__(576) void k_cr_inv0_96(double2* __restrict__ pool, 
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
     const int row = ti * 16 + lk + 4 * rr, col = tj * 16 + lr;
-    Mo[(int64_t)row * BP + col] = make_double2(sr[rr], si[rr]);
-    Mo[(int64_t)row * BP + HP + col] = make_double2(yr[rr], yi[rr]);
+    st16<ST>(Mo + (int64_t)row * BP + col, make_double2(sr[rr], si[rr]));
+    st16<ST>(Mo + (int64_t)row * BP + HP + col, make_double2(yr[rr], yi[rr]));
   }
   if (l == 0 && ti == tj) ldw[ti] = 0.5 * log(pp);
   __syncthreads();
@@ -784,7 +786,7 @@ __global__ __launch_bounds__(576) void k_cr_inv0_96(double2* __restrict__ pool, 
 // complement after one more register inversion; no pivoting, as i A is a
 // principal block of i D).  In place when dst == blk: every read precedes
 // the wave's first store.
-template <bool STATIC>
+template <bool STATIC, int ST>
 __device__ __forceinline__ void cr_inv32_wave(double2* __restrict__ pool, int64_t item, int bi, int li,
                                               const int* __restrict__ blk, const int* __restrict__ rblk,
                                               const int* __restrict__ dst, const int* __restrict__ slot,
@@ -839,12 +841,13 @@ __device__ __forceinline__ void cr_inv32_wave(double2* __restrict__ pool, int64_
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
     const int row = lk + 4 * rr;
-    Mo[(int64_t)row * BP + lr] = make_double2(sr[rr], si[rr]);
-    Mo[(int64_t)row * BP + HP + lr] = make_double2(yr[rr], yi[rr]);
+    st16<ST>(Mo + (int64_t)row * BP + lr, make_double2(sr[rr], si[rr]));
+    st16<ST>(Mo + (int64_t)row * BP + HP + lr, make_double2(yr[rr], yi[rr]));
   }
   if (l == 0) ldpart[(int64_t)bi * nslots + slot[li]] = ld + 0.5 * (log(pa) + log(ps));
 }
 
+template <int ST>
 __global__ __launch_bounds__(64) void k_cr_inv0_32(double2* __restrict__ pool, int64_t item,
                                                    const int* __restrict__ blk, const int* __restrict__ rblk,
                                                    const int* __restrict__ dst, int gcol,
@@ -859,10 +862,11 @@ __global__ __launch_bounds__(64) void k_cr_inv0_32(double2* __restrict__ pool, i
     if (bi % P == 0) inv0_site_guard(Delta + (int64_t)(bi / P) * 2 * N, site4, N, cap4, flag);
     return;
   }
-  cr_inv32_wave<true>(pool, item, bi, li, blk, rblk, dst, slot, ldpart, ldA, nslots);
+  cr_inv32_wave<true, ST>(pool, item, bi, li, blk, rblk, dst, slot, ldpart, ldA, nslots);
 }
 
 // gcol: the guard column's x (-1: no guard), as k_cr_inv
+template <int ST>
 __global__ __launch_bounds__(64) void k_cr_inv32(double2* __restrict__ pool, int64_t item,
                                                  const int* __restrict__ blk, const int* __restrict__ dst,
                                                  int gcol, const int* __restrict__ slot,
@@ -874,7 +878,7 @@ __global__ __launch_bounds__(64) void k_cr_inv32(double2* __restrict__ pool, int
     if (bi % P == 0) site_guard_wg(sg, N, bi / P);
     return;
   }
-  cr_inv32_wave<false>(pool, item, bi, li, blk, nullptr, dst, slot, ldpart, nullptr, nslots);
+  cr_inv32_wave<false, ST>(pool, item, bi, li, blk, nullptr, dst, slot, ldpart, nullptr, nslots);
 }
 
 // ---------------------------------------------------------------------------
@@ -1017,7 +1021,7 @@ __device__ __forceinline__ int64_t cr_slot_off(int v) {
 // at O (the lane's first output element; C likewise, cpf its values loaded at
 // tile start).  KSPLIT > 1: the waves of a tile sum their partials through LDS
 // (every wave of the workgroup reaches the barrier, valid or not).
-template <int BP, int MI, int KSPLIT>
+template <int BP, int MI, int KSPLIT, int ST = kStorePlain>
 __device__ __forceinline__ void cr_tile_store(d4 (&t1)[MI][MI], d4 (&t2)[MI][MI], d4 (&t3)[MI][MI], double sg,
                                               double2* O, bool hasc, const double2 (&cpf)[MI * MI * 4 / KSPLIT],
                                               bool valid, [[maybe_unused]] bool stamp = false) {
@@ -1029,7 +1033,7 @@ __device__ __forceinline__ void cr_tile_store(d4 (&t1)[MI][MI], d4 (&t2)[MI][MI]
       x.x += c.x;
       x.y += c.y;
     }
-    O[cr_slot_off<BP, MI>(v)] = x;
+    st16<ST>(O + cr_slot_off<BP, MI>(v), x);
   };
   // complex partial of register slot v
   auto partial = [&](int v) {
@@ -1090,7 +1094,7 @@ __device__ __forceinline__ void cr_tile_cin(const double2* C, double2 (&cpf)[MI 
 // TILESIGN: each task's sign from its descriptor (kCrNegBit; side-work task
 // lists mix stages of both signs) instead of sg.  PFX: operand prefetch depth
 // in k-steps (0: the default).
-template <int BP, int MI, int KSPLIT, int PFX = 0, bool TILESIGN = false>
+template <int BP, int MI, int KSPLIT, int PFX = 0, bool TILESIGN = false, int ST = kStorePlain>
 __device__ __forceinline__ void cr_gemm_wg(double2* __restrict__ pool, int64_t item,
                                            const CrTask* __restrict__ tasks, int ntasks, int maxt, int total,
                                            double sg, int g) {
@@ -1140,7 +1144,7 @@ __device__ __forceinline__ void cr_gemm_wg(double2* __restrict__ pool, int64_t i
       if (kq == 1) run(std::integral_constant<int, 1>{});
     }
   }
-  cr_tile_store<BP, MI, KSPLIT>(t1, t2, t3, sg, O, hasc, cpf, valid);
+  cr_tile_store<BP, MI, KSPLIT, ST>(t1, t2, t3, sg, O, hasc, cpf, valid);
 }
 
 // Argument order: what the first loads need leads (the build preloads the
@@ -1158,7 +1162,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 // of workgroup b takes slot b * TPW + w / KSPLIT with one 64-byte scalar load
 // and issues its operand loads right after it.  Empty slots (out == kCrNone)
 // pad the last workgroup.
-template <int BP, int KSPLIT>
+template <int BP, int KSPLIT, int ST>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGemmWaves))) void k_cr_gemm16(
     double2* __restrict__ pool, const CrSlot* __restrict__ slots, double sg) {
   constexpr int TPW = 4 / KSPLIT, NV = 4;
@@ -1223,9 +1227,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGemmWaves)
     }
   }
 #ifdef CR_GEMM_STAMPS
-  cr_tile_store<BP, 1, KSPLIT>(t1, t2, t3, sg, base + out + lo, hasc, cpf, valid, g_gemm_on);
+  cr_tile_store<BP, 1, KSPLIT, ST>(t1, t2, t3, sg, base + out + lo, hasc, cpf, valid, g_gemm_on);
 #else
-  cr_tile_store<BP, 1, KSPLIT>(t1, t2, t3, sg, base + out + lo, hasc, cpf, valid);
+  cr_tile_store<BP, 1, KSPLIT, ST>(t1, t2, t3, sg, base + out + lo, hasc, cpf, valid);
 #endif
 #ifdef CR_GEMM_STAMPS
   if (g_gemm_on) __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1250,7 +1254,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGemmWaves)
 // ---------------------------------------------------------------------------
 // arguments in first-use order: the inversion workgroups (the first
 // ninv x nbatch) need only the leading ones; nside: side-work workgroups
-template <int NT>
+// ST / STS: store policy of the inversions' / the side products' outputs
+template <int NT, int ST, int STS>
 __global__ __launch_bounds__(64 * NT) void k_cr_inv_side(double2* __restrict__ pool, int64_t item,
                                                          const int* __restrict__ blk,
                                                          const int* __restrict__ dst, int ninv, int nbatch,
@@ -1266,7 +1271,7 @@ __global__ __launch_bounds__(64 * NT) void k_cr_inv_side(double2* __restrict__ p
   if (b < nall) {
     // the batch items grouped per XCD (xcd_remap over the inversion range)
     const int bl = CR_XCD_ITEMS ? xcd_remap(b, nall) : b;
-    cr_inv_wg<NT>(pool, item, bl / ninv, bl - (bl / ninv) * ninv, blk, dst, slot, ldpart, nslots, pan, ldw);
+    cr_inv_wg<NT, ST>(pool, item, bl / ninv, bl - (bl / ninv) * ninv, blk, dst, slot, ldpart, nslots, pan, ldw);
     return;
   }
   CR_STAMP_INIT(blk);
@@ -1278,7 +1283,7 @@ __global__ __launch_bounds__(64 * NT) void k_cr_inv_side(double2* __restrict__ p
     CR_STAMP_AT(31, 3ull);
     return;
   }
-  cr_gemm_wg<16 * NT, 2, 1, 0, true>(pool, item, stasks, nst, maxt, total, 1.0, xcd_remap(b - nall, nside));
+  cr_gemm_wg<16 * NT, 2, 1, 0, true, STS>(pool, item, stasks, nst, maxt, total, 1.0, xcd_remap(b - nall, nside));
 #ifdef CR_STAMPS
   if (stamp_on) __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -1302,6 +1307,7 @@ __global__ __launch_bounds__(64 * NT) void k_cr_inv_side(double2* __restrict__ p
 // creation so the G loads wait for one index load, not two.
 // arguments in first-use order (kernel-argument preload)
 constexpr int kPfLanes = 32;   // lanes per bond (poles strided over them)
+template <int ST>
 __global__ __launch_bounds__(256) void k_cr_pair_force(
     double2* __restrict__ pool, int64_t item, const int64_t* __restrict__ bond4, int N, int P,
     const double* __restrict__ cpole, double2* __restrict__ Delta, double2* __restrict__ Pair,
@@ -1348,8 +1354,8 @@ __global__ __launch_bounds__(256) void k_cr_pair_force(
     // (Dsrc: the one the reference's overwrite order leaves, src/Hamiltonian.jl:68-83)
     for (int q = sub; q < P; q += LB) {
       double2* G = pool + (int64_t)(c * P + q) * item;
-      if (p1 >= 0) G[p1] = dn;
-      if (p2 >= 0) G[p2] = dn;
+      if (p1 >= 0) st16<ST>(G + p1, dn);
+      if (p2 >= 0) st16<ST>(G + p2, dn);
     }
   }
 }
@@ -1409,13 +1415,16 @@ __global__ __launch_bounds__(256) void k_cr_fermion_energy(const double2* __rest
 // ---------------------------------------------------------------------------
 void launch_cr_inv0(const CrDims& c, double2* pool, const int* blk, const int* rblk, const int* dst,
                     const int* slot, int n, double* ldpart, const double* ldA, hipStream_t s,
-                    const double2* Delta, const int* site4, double cap4, int* flag) {
+                    const double2* Delta, const int* site4, double cap4, int* flag, int store) {
   if (n <= 0) return;
   const bool guard = Delta != nullptr && site4 != nullptr && flag != nullptr;
-  hipLaunchKernelGGL(c.BP == 32 ? k_cr_inv0_32 : c.BP == 96 ? k_cr_inv0_96 : k_cr_inv0,
-                     dim3(n + (guard ? 1 : 0), c.nbatch), dim3(c.BP == 32 ? 64 : c.BP == 96 ? 576 : 256), 0, s, pool,
-                     c.item, blk, rblk, dst, guard ? n : -1, slot, ldpart, ldA, c.Ly, guard ? Delta : nullptr, site4,
-                     c.N, c.P, cap4, flag);
+  with_store(store, [&](auto st) {
+    constexpr int ST = decltype(st)::value;
+    hipLaunchKernelGGL(c.BP == 32 ? k_cr_inv0_32<ST> : c.BP == 96 ? k_cr_inv0_96<ST> : k_cr_inv0<ST>,
+                       dim3(n + (guard ? 1 : 0), c.nbatch), dim3(c.BP == 32 ? 64 : c.BP == 96 ? 576 : 256), 0, s, pool,
+                       c.item, blk, rblk, dst, guard ? n : -1, slot, ldpart, ldA, c.Ly, guard ? Delta : nullptr,
+                       site4, c.N, c.P, cap4, flag);
+  });
 }
 
 void launch_cr_fill(const CrDims& c, double2* pool, const int* list, int nlist, const int* hcol,
@@ -1431,73 +1440,85 @@ void launch_cr_fill(const CrDims& c, double2* pool, const int* list, int nlist, 
 }
 
 void launch_cr_inv(const CrDims& c, double2* pool, const int* blk, const int* dst, const int* slot,
-                   int n, double* ldpart, hipStream_t s, const SiteGuard& sg) {
+                   int n, double* ldpart, hipStream_t s, const SiteGuard& sg, int store) {
   if (n <= 0) return;
   const bool guard = sg.Delta != nullptr;
   const dim3 g(n + (guard ? 1 : 0), c.nbatch);
   const int gcol = guard ? n : -1;
-  switch (c.BP) {
-    case 32:
-      if (c.inv32)
-        hipLaunchKernelGGL(k_cr_inv32, g, dim3(64), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly, sg, c.N,
-                           c.P);
-      else
-        hipLaunchKernelGGL(k_cr_inv<2>, g, dim3(128), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly, sg,
+  with_store(store, [&](auto st) {
+    constexpr int ST = decltype(st)::value;
+    switch (c.BP) {
+      case 32:
+        if (c.inv32)
+          hipLaunchKernelGGL(k_cr_inv32<ST>, g, dim3(64), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly, sg,
+                             c.N, c.P);
+        else
+          hipLaunchKernelGGL((k_cr_inv<2, ST>), g, dim3(128), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly,
+                             sg, c.N, c.P);
+        break;
+      case 64:
+        hipLaunchKernelGGL((k_cr_inv<4, ST>), g, dim3(256), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly, sg,
                            c.N, c.P);
-      break;
-    case 64:
-      hipLaunchKernelGGL(k_cr_inv<4>, g, dim3(256), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly, sg, c.N,
-                         c.P);
-      break;
-    case 96:
-      hipLaunchKernelGGL(k_cr_inv<6>, g, dim3(384), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly, sg, c.N,
-                         c.P);
-      break;
-    default:
-      hipLaunchKernelGGL(k_cr_inv<8>, g, dim3(512), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly, sg, c.N,
-                         c.P);
-      break;
-  }
+        break;
+      case 96:
+        hipLaunchKernelGGL((k_cr_inv<6, ST>), g, dim3(384), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly, sg,
+                           c.N, c.P);
+        break;
+      default:
+        hipLaunchKernelGGL((k_cr_inv<8, ST>), g, dim3(512), 0, s, pool, c.item, blk, dst, gcol, slot, ldpart, c.Ly, sg,
+                           c.N, c.P);
+        break;
+    }
+  });
 }
 
 void launch_cr_inv_side(const CrDims& c, double2* pool, const int* blk, const int* dst, const int* slot,
                         int n, double* ldpart, const CrTask* stasks, int nst, int maxt32, hipStream_t s,
-                        const SiteGuard& sg) {
+                        const SiteGuard& sg, int store, int store_side) {
   if (nst <= 0) {
-    launch_cr_inv(c, pool, blk, dst, slot, n, ldpart, s, sg);
+    launch_cr_inv(c, pool, blk, dst, slot, n, ldpart, s, sg, store);
     return;
   }
   const int total = c.nbatch * nst * maxt32;
   const int side_wg = (total + 3) / 4;
   const int nc = c.nbatch / c.P;
   const dim3 g(n * c.nbatch + side_wg + (sg.Delta != nullptr ? nc : 0));
-  hipLaunchKernelGGL(k_cr_inv_side<4>, g, dim3(256), 0, s, pool, c.item, blk, dst, n, c.nbatch, slot, ldpart,
-                     c.Ly, side_wg, stasks, nst, maxt32, total, sg, c.N);
+  with_store(store, [&](auto st) {
+    with_store(store_side, [&](auto sts) {
+      hipLaunchKernelGGL((k_cr_inv_side<4, decltype(st)::value, decltype(sts)::value>), g, dim3(256), 0, s, pool,
+                         c.item, blk, dst, n, c.nbatch, slot, ldpart, c.Ly, side_wg, stasks, nst, maxt32, total, sg,
+                         c.N);
+    });
+  });
 }
 
 void launch_cr_gemm(const CrDims& c, double2* pool, const CrTask* tasks, int ntasks, int maxt32,
                     int maxt16, const CrSlot* slots, int nslot_wgs, const CrGemmCfg& cfg, double sg,
-                    hipStream_t s) {
+                    hipStream_t s, int store) {
   (void)maxt16;
   if (ntasks <= 0) return;
   const dim3 b(256);
   if (cfg.ts == 16) {
     const dim3 g(nslot_wgs);
-#define CR_GEMM16(BPV, KSV) hipLaunchKernelGGL((k_cr_gemm16<BPV, KSV>), g, b, 0, s, pool, slots, sg)
+#define CR_GEMM16(BPV, KSV) hipLaunchKernelGGL((k_cr_gemm16<BPV, KSV, ST>), g, b, 0, s, pool, slots, sg)
 #define CR_GEMM16_BP(BPV)                        \
   if (cfg.ksplit == 4) CR_GEMM16(BPV, 4);        \
   else if (cfg.ksplit == 2) CR_GEMM16(BPV, 2);   \
   else CR_GEMM16(BPV, 1);
-    switch (c.BP) {
-      case 32: CR_GEMM16_BP(32) break;
-      case 64: CR_GEMM16_BP(64) break;
-      case 96: CR_GEMM16_BP(96) break;
-      default: CR_GEMM16_BP(128) break;
-    }
+    with_store(store, [&](auto st) {
+      constexpr int ST = decltype(st)::value;
+      switch (c.BP) {
+        case 32: CR_GEMM16_BP(32) break;
+        case 64: CR_GEMM16_BP(64) break;
+        case 96: CR_GEMM16_BP(96) break;
+        default: CR_GEMM16_BP(128) break;
+      }
+    });
 #undef CR_GEMM16_BP
 #undef CR_GEMM16
     return;
   }
+  // (the 32 x 32 tile configurations are A/B configurations: plain stores)
   const int total = c.nbatch * ntasks * maxt32;
   const int tpw = 4 / cfg.ksplit;
   const dim3 g((total + tpw - 1) / tpw);
@@ -1518,11 +1539,14 @@ void launch_cr_gemm(const CrDims& c, double2* pool, const CrTask* tasks, int nta
 
 void launch_cr_pair_force(const CrDims& c, double2* pool, const int64_t* bond4, const double* cpole,
                           double2* Delta, double2* Pair, double2* F, double2* Pi,
-                          const KickDrift& kd, double beta, double J, hipStream_t s) {
+                          const KickDrift& kd, double beta, double J, hipStream_t s, int store) {
   const int nc = c.nbatch / c.P;
   constexpr int BPW = 256 / kPfLanes;   // bonds per workgroup
-  hipLaunchKernelGGL(k_cr_pair_force, dim3((2 * c.N + BPW - 1) / BPW, nc), dim3(256), 0, s, pool, c.item, bond4, c.N,
-                     c.P, cpole, Delta, Pair, F, Pi, kd.kick, kd.drift, kd.cap * kd.cap, kd.flag, beta, J);
+  with_store(store, [&](auto st) {
+    hipLaunchKernelGGL(k_cr_pair_force<decltype(st)::value>, dim3((2 * c.N + BPW - 1) / BPW, nc), dim3(256), 0, s,
+                       pool, c.item, bond4, c.N, c.P, cpole, Delta, Pair, F, Pi, kd.kick, kd.drift, kd.cap * kd.cap,
+                       kd.flag, beta, J);
+  });
 }
 
 void launch_cr_fermion_energy(const CrDims& c, const double2* pool, const int64_t* doff,

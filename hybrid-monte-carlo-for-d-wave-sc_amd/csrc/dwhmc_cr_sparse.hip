@@ -137,8 +137,10 @@ __device__ __forceinline__ void wave_sync() {
 __device__ __forceinline__ double2 sp_ld(const double2* base, unsigned off) {
   return *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(base) + off);
 }
+// ST: the store policy of a pool store (st16); the staged LDS rows stay plain
+template <int ST = kStorePlain>
 __device__ __forceinline__ void sp_st(double2* base, unsigned off, double2 v) {
-  *reinterpret_cast<double2*>(reinterpret_cast<char*>(base) + off) = v;
+  st16<ST>(reinterpret_cast<double2*>(reinterpret_cast<char*>(base) + off), v);
 }
 
 // Column data of the sparse right operands (dense . sparse products): every
@@ -217,7 +219,7 @@ struct ColStage {
 // forward: one wave per output row r of the kept row k's D', U', L'.  The
 // record load is followed by the Δ load of the three pairing slots and every
 // dense element load at once; the V rows meet in LDS.
-template <int BP>
+template <int BP, int ST>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesF<BP>))) void k_cr_sp_fwd(
     double2* __restrict__ pool, int64_t item, const CrSpRowFwd* __restrict__ recs, const double2* __restrict__ tcv,
     const int* __restrict__ tcm, const double2* __restrict__ Delta, int twoN, int P) {
@@ -286,9 +288,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesF<B
       cmac(u, sp_ld(sc[w][0], kr), vr);
     }
     if (l + 64 * j < BP) {
-      sp_st(base, t.od + cl[j], d);
-      sp_st(base, t.ou + cl[j], u);
-      sp_st(base, t.ol + cl[j], lo);
+      sp_st<ST>(base, t.od + cl[j], d);
+      sp_st<ST>(base, t.ou + cl[j], u);
+      sp_st<ST>(base, t.ol + cl[j], lo);
     }
   }
 }
@@ -297,7 +299,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesF<B
 // Y_a, Y_c and M = Y_a U_a + Y_c L_e (RPW rows in turn).  Row r of each G
 // block is staged in the wave's LDS (Z gathers from it), full rows of the G
 // blocks feed Y.
-template <int BP, int RPW>
+template <int BP, int RPW, int ST>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesB<BP>))) void k_cr_sp_bwd(
     double2* __restrict__ pool, int64_t item, const CrSpRowBwd* __restrict__ recs, const double2* __restrict__ tcv,
     const int* __restrict__ tcm, const double2* __restrict__ Delta, int twoN, int P) {
@@ -406,10 +408,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesB<B
         cmac(zc, sp_ld(gr[w][3], ke), we);
       }
       if (l + 64 * j < BP) {
-        sp_st(base, t.oya + cl[j], yk[j][0]);
-        sp_st(base, t.oyc + cl[j], yk[j][1]);
-        sp_st(base, t.oza + cl[j], za);
-        sp_st(base, t.ozc + cl[j], zc);
+        sp_st<ST>(base, t.oya + cl[j], yk[j][0]);
+        sp_st<ST>(base, t.oyc + cl[j], yk[j][1]);
+        sp_st<ST>(base, t.oza + cl[j], za);
+        sp_st<ST>(base, t.ozc + cl[j], zc);
       }
     }
     wave_sync();   // every lane's Z gathers from gr[w] are done
@@ -430,7 +432,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesB<B
         cmac(mx, sp_ld(sc[w][0], ci[0][e][c]), cv[0][e][c]);
         cmac(mx, sp_ld(sc[w][1], ci[1][e][c]), cv[1][e][c]);
       }
-      if (l + 64 * j < BP) sp_st(base, t.omx + cl[j], mx);
+      if (l + 64 * j < BP) sp_st<ST>(base, t.omx + cl[j], mx);
     }
     if (RPW > 1) wave_sync();   // the M gathers are done before the next row's G rows land
   }
@@ -439,26 +441,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSpWavesB<B
 }  // namespace
 
 void launch_cr_sp_fwd(const CrDims& c, double2* pool, const CrSpRowFwd* recs, int n, const double2* tcv,
-                      const int* tcm, const double2* Delta, hipStream_t s) {
+                      const int* tcm, const double2* Delta, hipStream_t s, int store) {
   if (n <= 0) return;
   const dim3 g(n * (c.BP / 2 / kSpRowsWG), c.nbatch), b(64 * kSpRowsWG);
-  switch (c.BP) {
-    case 32: hipLaunchKernelGGL(k_cr_sp_fwd<32>, g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
-    case 64: hipLaunchKernelGGL(k_cr_sp_fwd<64>, g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
-    default: hipLaunchKernelGGL(k_cr_sp_fwd<96>, g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
-  }
+  with_store(store, [&](auto st) {
+    constexpr int ST = decltype(st)::value;
+    switch (c.BP) {
+      case 32: hipLaunchKernelGGL((k_cr_sp_fwd<32, ST>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+      case 64: hipLaunchKernelGGL((k_cr_sp_fwd<64, ST>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+      default: hipLaunchKernelGGL((k_cr_sp_fwd<96, ST>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+    }
+  });
 }
 
 void launch_cr_sp_bwd(const CrDims& c, double2* pool, const CrSpRowBwd* recs, int n, const double2* tcv,
-                      const int* tcm, const double2* Delta, hipStream_t s) {
+                      const int* tcm, const double2* Delta, hipStream_t s, int store) {
   if (n <= 0) return;
   constexpr int RPW = SP_RPW_B;
   const dim3 g(n * (c.BP / 2 / (kSpRowsWG * RPW)), c.nbatch), b(64 * kSpRowsWG);
-  switch (c.BP) {
-    case 32: hipLaunchKernelGGL((k_cr_sp_bwd<32, RPW>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
-    case 64: hipLaunchKernelGGL((k_cr_sp_bwd<64, RPW>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
-    default: hipLaunchKernelGGL((k_cr_sp_bwd<96, RPW>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
-  }
+  with_store(store, [&](auto st) {
+    constexpr int ST = decltype(st)::value;
+    switch (c.BP) {
+      case 32: hipLaunchKernelGGL((k_cr_sp_bwd<32, RPW, ST>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+      case 64: hipLaunchKernelGGL((k_cr_sp_bwd<64, RPW, ST>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+      default: hipLaunchKernelGGL((k_cr_sp_bwd<96, RPW, ST>), g, b, 0, s, pool, c.item, recs, tcv, tcm, Delta, 2 * c.N, c.P); break;
+    }
+  });
 }
 
 }  // namespace dwh

@@ -65,6 +65,32 @@ __device__ __forceinline__ double2 cinv_fast(double2 a) {
   return make_double2(a.x * s, -a.y * s);
 }
 
+// One 16-byte store of a CR pool element with a cache policy (the values of
+// dwh::kStore*, dwhmc_internal.h; a compile-time parameter of each kernel
+// instantiation, chosen per stage by the plan).  The value stored is the same
+// under every policy; only where the line lives afterwards differs:
+//   plain    global_store_dwordx4: the line stays dirty in this XCD's L2 and
+//            is written back at the end of the launch (the release every
+//            dependent launch ends with);
+//   through  two relaxed agent-scope 8-byte stores (global_store_dwordx2 sc1):
+//            written through while the kernel runs, the L2 drops the line;
+//   stream   non-temporal (global_store_dwordx4 nt): the line is marked for
+//            early eviction but stays in the L2.
+template <int POL>
+__device__ __forceinline__ void st16(double2* p, double2 v) {
+  if constexpr (POL == 1) {
+    double* q = reinterpret_cast<double*>(p);
+    __hip_atomic_store(q, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(q + 1, v.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else if constexpr (POL == 2) {
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    __builtin_nontemporal_store(v2d{v.x, v.y}, reinterpret_cast<v2d*>(p));
+  } else {
+    static_assert(POL == 0, "store policy: 0 plain, 1 write-through, 2 non-temporal");
+    *p = v;
+  }
+}
+
 // Bijective XCD-aware remap of a 1D grid (cdna_hip_programming.md §5): blocks
 // b and b+8 share an XCD, so item ranges [x*q, (x+1)*q) are given to one XCD
 // and neighbouring rows of one matrix share that XCD's L2.  Speed only.

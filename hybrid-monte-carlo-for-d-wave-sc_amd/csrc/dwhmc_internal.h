@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace dwh {
 
 constexpr int kGJ = 64;        // Gauss-Jordan block (rows/cols of one diagonal block)
@@ -88,6 +90,18 @@ inline int cr_task_tiles(const CrTask& t, int ts) {
   return ((t.r1 + ts - 1) / ts - t.r0 / ts) * ((t.c1 + ts - 1) / ts - t.c0 / ts);
 }
 inline bool cr_supported_bp(int BP) { return BP == 32 || BP == 64 || BP == 96 || BP == 128; }
+// Cache policy of a launch's pool stores (st16, dwhmc_device.h): a template
+// argument of the kernels, picked per stage by the plan (CrStage::store)
+constexpr int kStorePlain = 0, kStoreThrough = 1, kStoreStream = 2;
+// launchers: f(std::integral_constant<int, ST>{}) for the run-time policy.
+// The kernels are built for the policies the plan can pick, plain and
+// write-through; non-temporal stores won in no family
+// (profiles/r07_store_policy_ab.txt), and adding the branch here builds them.
+template <class F>
+inline void with_store(int store, F&& f) {
+  if (store == kStoreThrough) f(std::integral_constant<int, kStoreThrough>{});
+  else f(std::integral_constant<int, kStorePlain>{});
+}
 // diagnostic stamp builds (-DCR_STAMPS, dwh_debug_cr_stamps): workgroups recorded per launch
 constexpr int kCrStampWG = 2048;
 #ifdef CR_STAMPS
@@ -106,7 +120,7 @@ void launch_cr_fill(const CrDims& c, double2* pool, const int* list, int nlist, 
 // Δ/2 is also scattered into those level-0 entries (k_cr_fill's scatter)
 void launch_cr_pair_force(const CrDims& c, double2* pool, const int64_t* bond4, const double* cpole,
                           double2* Delta, double2* Pair, double2* F, double2* Pi,
-                          const KickDrift& kd, double beta, double J, hipStream_t s);
+                          const KickDrift& kd, double beta, double J, hipStream_t s, int store = kStorePlain);
 // E_f and Tr ρ_hh from the CR block pivots and the G22 diagonal (pool offsets doff)
 // part: 2 x nbatch scratch, done: nchains counters (zero at creation; the
 // kernel leaves them zero)
@@ -124,7 +138,7 @@ struct SiteGuard {
   int* flag = nullptr;
 };
 void launch_cr_inv(const CrDims& c, double2* pool, const int* blk, const int* dst, const int* slot,
-                   int n, double* ldpart, hipStream_t s, const SiteGuard& sg = SiteGuard{});
+                   int n, double* ldpart, hipStream_t s, const SiteGuard& sg = SiteGuard{}, int store = kStorePlain);
 // level-0 inversions of blocks blk[i] (BP = 32, 64, 96) from the static R = A^-1
 // blocks rblk[i] (k_cr_inv0); ln|det| = ldA/2 + ln|det S| into ldpart slots
 inline bool cr_supported_inv0(int BP) { return BP == 64 || BP == 32 || BP == 96; }
@@ -133,14 +147,14 @@ inline bool cr_supported_inv0(int BP) { return BP == 64 || BP == 32 || BP == 96;
 void launch_cr_inv0(const CrDims& c, double2* pool, const int* blk, const int* rblk, const int* dst,
                     const int* slot, int n, double* ldpart, const double* ldA, hipStream_t s,
                     const double2* Delta = nullptr, const int* site4 = nullptr, double cap4 = 0.0,
-                    int* flag = nullptr);
+                    int* flag = nullptr, int store = kStorePlain);
 // the same inversions plus nst side-work product tasks per batch item
 // (32 x 32 wave tiles, maxt32 per task, each task's sign in bq & kCrNegBit)
 // on the CUs the inversions leave idle
 inline bool cr_supported_side(int BP) { return BP == 64; }
 void launch_cr_inv_side(const CrDims& c, double2* pool, const int* blk, const int* dst, const int* slot,
                         int n, double* ldpart, const CrTask* stasks, int nst, int maxt32, hipStream_t s,
-                        const SiteGuard& sg = SiteGuard{});
+                        const SiteGuard& sg = SiteGuard{}, int store = kStorePlain, int store_side = kStorePlain);
 // Sparse level-0 stages (dwhmc_cr_sparse.hip): the level-0 U / L blocks have
 // at most kCrSpNZ nonzeros per row and column (vertical hopping + one pairing
 // entry); rowpat / colpat hold them per pool block ([block][entry][BP], entry
@@ -198,9 +212,9 @@ static_assert(sizeof(CrSpRowFwd) == 256 && sizeof(CrSpRowBwd) == 256, "one recor
 // applied, and meta = (Δ index + 1, 0 none) | op << 22 | row << 24.
 // Delta: the chains' N x 2 Δ (batch item bi reads chain bi / P).
 void launch_cr_sp_fwd(const CrDims& c, double2* pool, const CrSpRowFwd* recs, int n, const double2* tcv,
-                      const int* tcm, const double2* Delta, hipStream_t s);
+                      const int* tcm, const double2* Delta, hipStream_t s, int store = kStorePlain);
 void launch_cr_sp_bwd(const CrDims& c, double2* pool, const CrSpRowBwd* recs, int n, const double2* tcv,
-                      const int* tcm, const double2* Delta, hipStream_t s);
+                      const int* tcm, const double2* Delta, hipStream_t s, int store = kStorePlain);
 // block-product stage configuration: output tile TS x TS (16 or 32) and the
 // number of waves splitting each tile's K range (1, 2, 4)
 struct CrGemmCfg {
@@ -210,7 +224,7 @@ struct CrGemmCfg {
 // slots: the stage's cr_gemm_slots (16 x 16 stages, dwhmc_plan.h); tasks: 32 x 32 stages
 void launch_cr_gemm(const CrDims& c, double2* pool, const CrTask* tasks, int ntasks, int maxt32,
                     int maxt16, const CrSlot* slots, int nslot_wgs, const CrGemmCfg& cfg, double sg,
-                    hipStream_t s);
+                    hipStream_t s, int store = kStorePlain);
 
 // dense h - i y_q (padded with identity) for every (chain, pole): R init input
 void launch_fill_hz(const Dims& d, double2* M, const int* hcol, const double* hval,

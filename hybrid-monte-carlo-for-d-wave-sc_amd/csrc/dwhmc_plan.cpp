@@ -1053,6 +1053,103 @@ void cr_gemm_slots(const CrDims& c, const CrTile* tl16, int ntl16, const CrGemmC
     }
 }
 
+std::vector<CrStageStores> cr_stage_stores(const CrPlan& pl, int BP) {
+  const int ns = (int)pl.stages.size();
+  const int64_t BB = (int64_t)(BP / 2) * BP, blk_bytes = BB * (int64_t)sizeof(double2);
+  // per stage: the blocks it reads; its own outputs and its side products with their bytes
+  typedef std::vector<std::pair<int, int64_t>> Writes;
+  std::vector<std::vector<int>> rd(ns + 1);
+  std::vector<Writes> wr(ns), wrs(ns);
+  auto task_reads = [](const dwh::CrTask& t, std::vector<int>& r) {
+    for (int h = 0; h < t.nt; ++h) {
+      r.push_back(t.a[h]);
+      r.push_back(t.b[h]);
+    }
+    if (t.cin >= 0) r.push_back(t.cin);
+  };
+  for (int si = 0; si < ns; ++si) {
+    const CrStage& st = pl.stages[si];
+    if (st.kind == 0) {
+      for (int k = 0; k < st.n; ++k) {
+        rd[si].push_back(pl.inv_blk[st.first + k]);
+        wr[si].push_back({pl.inv_dst[st.first + k], blk_bytes});
+      }
+      if (st.l0) rd[si].insert(rd[si].end(), pl.inv0_r.begin(), pl.inv0_r.end());
+      for (int k = 0; k < st.ntiles; ++k) {
+        task_reads(pl.tasks[st.tfirst + k], rd[si]);
+        wrs[si].push_back({pl.tasks[st.tfirst + k].out, blk_bytes});
+      }
+    } else if (st.kind == 2) {
+      for (int k = 0; k < st.n; ++k) {
+        if (st.sp == 0) {
+          const dwh::CrSpFwd& t = pl.sp_fwd[st.first + k];
+          for (int b : {t.dk, t.uk, t.lk, t.uel, t.lel, t.uer, t.ler, t.dir, t.dil}) rd[si].push_back(b);
+          for (int b : {t.od, t.ou, t.ol}) wr[si].push_back({b, blk_bytes});
+        } else {
+          const dwh::CrSpBwd& t = pl.sp_bwd[st.first + k];
+          for (int b : {t.gaa, t.gac, t.gca, t.gcc, t.ua, t.le, t.la, t.ue}) rd[si].push_back(b);
+          for (int b : {t.oza, t.ozc, t.oya, t.oyc, t.omx}) wr[si].push_back({b, blk_bytes});
+        }
+      }
+    } else {
+      for (int k = 0; k < st.n; ++k) task_reads(pl.tasks[st.first + k], rd[si]);
+      for (int k = 0; k < st.ntiles; ++k)
+        wr[si].push_back({pl.tiles16[st.tfirst + k].out, 256 * (int64_t)sizeof(double2)});
+    }
+  }
+  // the force gather is the launch after the last stage
+  for (int64_t o : pl.goff)
+    if (o >= 0) rd[ns].push_back((int)(o / BB));
+  for (auto& r : rd) {
+    std::sort(r.begin(), r.end());
+    r.erase(std::unique(r.begin(), r.end()), r.end());
+  }
+  std::vector<CrStageStores> out(ns);
+  for (int si = 0; si < ns; ++si) {
+    auto tally = [&](const Writes& w, int64_t* bytes, int64_t* next, int* first) {
+      for (const auto& bw : w) {
+        int d = kCrNeverRead;
+        for (int sj = si + 1; sj <= ns && d == kCrNeverRead; ++sj)
+          if (std::binary_search(rd[sj].begin(), rd[sj].end(), bw.first)) d = sj - si;
+        *bytes += bw.second;
+        if (d == 1) *next += bw.second;
+        *first = std::min(*first, d);
+      }
+    };
+    tally(wr[si], &out[si].bytes, &out[si].bytes_next, &out[si].first_read);
+    tally(wrs[si], &out[si].bytes_side, &out[si].bytes_side_next, &out[si].first_read_side);
+  }
+  return out;
+}
+
+namespace {
+// Store policy of every launch (CrStage::store / store_side,
+// CrPlan::store_force), by family as measured at C3 / C2 / C5 (DESIGN.md §4
+// "Store policy", profiles/r07_store_policy_ab.txt): write-through for the
+// product stages with a K split — the short launches of the coarse levels,
+// whose epilogue already stores 8-byte pieces, so the two sc1 stores cost no
+// instruction, and whose dirty lines no longer wait for the release that ends
+// the launch — and for the side products of the inversion launches (issued
+// beside the 16 us inversions, mostly read two or more launches later);
+// plain for everything else: the bandwidth-bound sparse stages and the
+// products without a K split lose to the 8-byte stores, the inversions and
+// the force scatter do not move, and non-temporal stores won nowhere.
+// DWHMC_CR_STORE=0: plain everywhere (A/B runs, tests); read at every context
+// creation.
+void cr_store_policies(CrPlan& pl) {
+  const char* e = std::getenv("DWHMC_CR_STORE");
+  const bool on = !(e && *e == '0');
+  for (CrStage& st : pl.stages) {
+    st.store = st.store_side = dwh::kStorePlain;
+    if (!on) continue;
+    if (st.kind == 0 && st.ntiles > 0) st.store_side = dwh::kStoreThrough;
+    // (the 32 x 32 tile configurations, A/B only, store plain)
+    if (st.kind == 1 && st.cfg.ts == 16 && st.cfg.ksplit > 1) st.store = dwh::kStoreThrough;
+  }
+  pl.store_force = dwh::kStorePlain;
+}
+}  // namespace
+
 void cr_plan_dump(const CrPlan& pl, int64_t nbatch, bool cfg) {
   const char* e = std::getenv("DWHMC_CR_PLAN_DUMP");
   if (!e || *e != '1') return;
@@ -1111,6 +1208,7 @@ int plan_cr(int64_t Lx, int64_t Ly, int P, int nbatch, const std::vector<int>& D
     pl.slots.resize(pl.slots.size() + (size_t)st.nswg * (4 / st.cfg.ksplit));
     cr_gemm_slots(c, pl.tiles16.data() + st.tfirst, st.ntiles, st.cfg, pl.slots.data() + st.sfirst);
   }
+  cr_store_policies(pl);
   return DWH_OK;
 }
 
@@ -1282,6 +1380,37 @@ int dwh_debug_cr_plan_check(int64_t Lx, int64_t Ly, int64_t nbatch, int32_t side
     stats[3] = ngemm;
     stats[4] = ntask;
     stats[5] = pl.nblk;
+  }
+  return DWH_OK;
+}
+
+// Per stage of the same plan, 10 values in out[10 i ..] (cap: stages out
+// holds; *nstages: the plan's): kind (0 inversion, 1 products, 2 sparse
+// forward, 3 sparse backward), the products' K split, bytes written per batch
+// item by the stage's own outputs / its side products, launches until the
+// first read of either (CrStageStores), the two store policies, and the bytes
+// of either that the very next launch reads.
+int dwh_debug_cr_plan_stores(int64_t Lx, int64_t Ly, int64_t nbatch, int32_t side, int32_t inv0, int64_t* out,
+                             int64_t cap, int64_t* nstages) {
+  if (!out || !nstages || cap < 0) return fail(nullptr, DWH_ERR_ARG, "bad output");
+  CrDims c;
+  CrPlan pl;
+  if (int rc = plan_periodic(Lx, Ly, nbatch, side, inv0, &c, &pl)) return rc;
+  const std::vector<CrStageStores> ss = cr_stage_stores(pl, c.BP);
+  *nstages = (int64_t)pl.stages.size();
+  for (int64_t i = 0; i < *nstages && i < cap; ++i) {
+    const CrStage& st = pl.stages[i];
+    int64_t* o = out + 10 * i;
+    o[0] = st.kind == 2 ? 2 + st.sp : st.kind;
+    o[1] = st.kind == 1 ? st.cfg.ksplit : 0;
+    o[2] = ss[i].bytes;
+    o[3] = ss[i].bytes_side;
+    o[4] = ss[i].first_read;
+    o[5] = ss[i].first_read_side;
+    o[6] = st.store;
+    o[7] = st.store_side;
+    o[8] = ss[i].bytes_next;
+    o[9] = ss[i].bytes_side_next;
   }
   return DWH_OK;
 }

@@ -30,6 +30,8 @@ struct CrStage {
   int sfirst = 0, nswg = 0;   // 16 x 16 products: their dispatch-ordered slots (CrPlan::slots, nswg workgroups)
   int l0 = 0;           // inversions: level 0 from the static R = A^-1 blocks (k_cr_inv0)
   int sp = 0;           // kind 2 (sparse level-0 stage): 0 forward (CrPlan::sp_fwd), 1 backward (sp_bwd)
+  int store = dwh::kStorePlain;        // cache policy of the launch's pool stores (cr_store_policies)
+  int store_side = dwh::kStorePlain;   // inversions with side work: of the side products' stores
 };
 
 struct CrPlan {
@@ -50,7 +52,22 @@ struct CrPlan {
   std::vector<dwh::CrSpFwd> sp_fwd;
   std::vector<dwh::CrSpBwd> sp_bwd;
   std::vector<int> rowpat, colpat;
+  int store_force = dwh::kStorePlain;   // k_cr_pair_force's Δ/2 scatter into the level-0 blocks
 };
+
+// What one launch of the step leaves behind: the bytes a stage writes per
+// batch item (whole blocks for the inversions, the sparse stages and the side
+// products; the 16 x 16 tiles of a product stage) and how many launches later
+// the first of them is read (1: by the very next launch; the force gather
+// follows the last stage; kCrNeverRead: by nothing the step launches) and how
+// many of the bytes the very next launch reads, for the stage's own outputs
+// and for its side products.
+constexpr int kCrNeverRead = 1 << 20;
+struct CrStageStores {
+  int64_t bytes = 0, bytes_side = 0, bytes_next = 0, bytes_side_next = 0;
+  int first_read = kCrNeverRead, first_read_side = kCrNeverRead;
+};
+std::vector<CrStageStores> cr_stage_stores(const CrPlan& pl, int BP);
 
 // The sparse stages' per-task operand arrays (launch_cr_sp_fwd / _bwd,
 // dwhmc_internal.h).  Per task: one host-resolved record per output row
@@ -105,7 +122,8 @@ int choose_algo(int32_t algo_req, int64_t Lx, int64_t Ly, AlgoChoice* out);
 // stages.  side / inv0: side work on the inversion launches / level-0
 // inversions from the static R blocks, where the block size supports them;
 // kCrFromEnv: on unless DWHMC_CR_SIDE=0 / DWHMC_CR_INV0=0 (A/B runs, tests).
-// DWHMC_CR_INV32=0: BP = 32 inversions by k_cr_inv<2>.  DWH_ERR_ARG: a lattice
+// DWHMC_CR_INV32=0: BP = 32 inversions by k_cr_inv<2>.  DWHMC_CR_STORE=0: every
+// launch stores plain (else the plan's store policies).  DWH_ERR_ARG: a lattice
 // row too wide, or a batch item of 2^32 elements or more.
 constexpr int kCrFromEnv = -1;
 int plan_cr(int64_t Lx, int64_t Ly, int P, int nbatch, const std::vector<int>& Dcol, const std::vector<int>& hcol,

@@ -593,6 +593,17 @@ int dwh_debug_cr_plan_check(int64_t Lx, int64_t Ly, int64_t nbatch, int32_t side
  * output windows).  flops[1] + flops[2] does not depend on `side`. */
 int dwh_debug_cr_plan_flops(int64_t Lx, int64_t Ly, int64_t nbatch, int32_t side, int32_t inv0, double* flops);
 
+/* What each launch of the same plan stores (host only): 10 values per stage in
+ * out[10 i ..] (cap: stages out can hold; *nstages: the plan's count) — kind
+ * (0 inversion, 1 products, 2 / 3 sparse level-0 forward / backward), the
+ * products' K split, bytes per batch item written by the stage's own outputs
+ * and by its side products, launches until either is first read (1: the very
+ * next launch; the force gather follows the last stage; 2^20: not read within
+ * the step), the store policy (0 plain, 1 write-through, 2 non-temporal) of
+ * the two, and the bytes of the two that the very next launch reads. */
+int dwh_debug_cr_plan_stores(int64_t Lx, int64_t Ly, int64_t nbatch, int32_t side, int32_t inv0, int64_t* out,
+                             int64_t cap, int64_t* nstages);
+
 /* The ‖h‖ bound pole selection uses (host only; h = the static particle block
  * of src/Hamiltonian.jl:10-44 with w_i - mu on the diagonal, per chain):
  * out[0] Gershgorin, out[1] the Lanczos estimate, out[2] 1 if every chain

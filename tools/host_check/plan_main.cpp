@@ -9,7 +9,7 @@
 //
 // It links dwhmc_plan.cpp and dwhmc_model.cpp only: that it links at all shows
 // the two files call nothing that needs a device or a vendor library.  Runs
-// dwh_debug_cr_plan_check and dwh_debug_cr_plan_flops over the lattices of
+// dwh_debug_cr_plan_check, _flops and _stores over the lattices of
 // tests/test_cr_plan_dataflow.py (both batch sizes, side / inv0 on and off,
 // DWHMC_CR_SPARSE0 and DWHMC_CR_MERGE both ways) and dwh_debug_h_bound for one
 // lattice.  Then the host side context creation runs, called directly:
@@ -418,6 +418,17 @@ int main() {
               expect(rf == DWH_OK && std::isfinite(fl[0] + fl[1] + fl[2]) && fl[0] > 0 && fl[1] >= 0 && fl[2] >= 0 &&
                          (side || fl[2] == 0.0),
                      "plan_flops", l[0], l[1], nbatch, side, inv0, sp, mg);
+              // what every stage stores: some bytes, and never more read by the next launch than written
+              std::vector<int64_t> ss(10 * (size_t)st[0]);
+              int64_t ns = 0;
+              bool ok = dwh_debug_cr_plan_stores(l[0], l[1], nbatch, side, inv0, ss.data(), st[0], &ns) == DWH_OK &&
+                        ns == st[0];
+              for (int64_t i = 0; ok && i < ns; ++i) {
+                const int64_t* o = &ss[10 * i];
+                ok = o[2] > 0 && o[8] >= 0 && o[8] <= o[2] && o[9] >= 0 && o[9] <= o[3] && o[4] >= 1 && o[6] >= 0 &&
+                     o[6] <= 2 && o[7] >= 0 && o[7] <= 2;
+              }
+              expect(ok, "plan_stores", l[0], l[1], nbatch, side, inv0, sp, mg);
             }
     }
   // a lattice row too wide for the CR path is refused, not planned
