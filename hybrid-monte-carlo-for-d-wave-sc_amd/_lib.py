@@ -93,6 +93,7 @@ SIGNATURES = {
     "dwh_spectral_window": (C.c_int, [_D, _D, _D, _I64, _I64, _I64, _P]),
     "dwh_measure_spectral_maps": (C.c_int, [_P, _I64, _I64, _P, _D, _D, _D, _I64, _I64, _I64, _P, _P]),
     "dwh_measure_current_response": (C.c_int, [_P, _I64, _I64, _P, _I32, _I64, _P, _I64, _P, _P]),
+    "dwh_debug_current_vertex": (C.c_int, [_I64, _I64, _D, _D, _P, _P, _I32, _I64, _P, _P]),
     "dwh_bench_response_product": (C.c_int, [_P, _I64, _DP]),
     "dwh_measure_operator_response": (C.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _D, _D, _D,
                                                 _I64, _P]),

@@ -582,6 +582,22 @@ def spectral_window(eta: float, domega: float, omega_max: float, first: int = 0,
     return omega
 
 
+def debug_current_vertex(Lx, Ly, t, tp, nn_table, nnn_table, direction="x", q=((0, 1),), lib=None) -> np.ndarray:
+    """The Nambu vertices J_α(q) = Jq ⊕ Jq that measure_current_response
+    uploads for this lattice (dwh_debug_current_vertex; host arithmetic, no
+    device), dense: (nq, 2N, 2N)."""
+    lib = _lib.load() if lib is None else lib
+    if direction not in ("x", "y", 0, 1):
+        raise ValueError("direction must be 'x' or 'y'")
+    qa = np.ascontiguousarray(np.asarray(q, dtype=np.int64).reshape(-1, 2))
+    n2 = 2 * int(Lx) * int(Ly)
+    out = np.empty((qa.shape[0], n2, n2), dtype=np.complex128)
+    nn, nnn = table_to_abi(nn_table), table_to_abi(nnn_table)
+    check(lib.dwh_debug_current_vertex(int(Lx), int(Ly), float(t), float(tp), ptr(nn), ptr(nnn),
+                                       0 if direction in ("x", 0) else 1, qa.shape[0], ptr(qa), ptr(out)))
+    return np.ascontiguousarray(np.transpose(out, (0, 2, 1)))   # (column-major on the ABI side)
+
+
 CR_KINDS = {"inv": 0, "inv0": 1, "gemm": 2, "inv_side": 3}
 
 

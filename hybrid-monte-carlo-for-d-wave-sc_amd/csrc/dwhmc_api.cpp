@@ -1,8 +1,8 @@
 // C-ABI context of the MI355X fermionic action/force path (include/dwhmc.h):
 // context creation, the leapfrog step (Gauss-Jordan / cyclic reduction / eig),
 // the guards with their pole re-selection, and the HMC and state entry points.
-// The context struct is in dwhmc_ctx.h, the eigensolver driver and the
-// transport measurement in dwhmc_measure.cpp.
+// The context struct is in dwhmc_ctx.h, the eigensolver driver in
+// dwhmc_eigsolve.cpp and the measurements in dwhmc_measure.cpp.
 //
 // Context creation is a sequence of host-only steps that live elsewhere — the
 // lattice model and the pole selection (dwhmc_model.cpp), the choice of

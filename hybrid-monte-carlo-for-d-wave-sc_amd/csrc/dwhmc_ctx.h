@@ -1,8 +1,9 @@
 // The C-ABI context (struct dwh_ctx) and the helpers every file that drives
 // the device shares: error returns, device allocation, the event timers, and
-// the few functions that cross between dwhmc_api.cpp (steps, creation, HMC)
-// and dwhmc_measure.cpp (eigensolver driver, transport).  Private to those
-// two files.  Not part of the public ABI.
+// the few functions that cross between dwhmc_api.cpp (steps, creation, HMC),
+// dwhmc_eigsolve.cpp (eigensolver driver) and dwhmc_measure.cpp (transport,
+// spectral maps, vertex responses).  Private to those files.  Not part of the
+// public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
@@ -142,28 +143,30 @@ struct dwh_ctx {
   // and the two maps' output tiles (N x kSpChunk each per state)
   int sp_slots = 0;
   double *d_sp_lam = nullptr, *d_sp_out = nullptr;
-  // current response (dwh_measure_current_response), allocated on first use,
+  // the vertex responses (current, one-body operator, Nambu cross response:
+  // vertex_prepare / vertex_run, dwhmc_measure.cpp), allocated on first use,
   // grown on demand and freed where the slot buffers are reallocated: d_rs_ws
-  // holds rs_mats n2 x n2 matrices (JU_q and J_nm(q) of one group of momenta,
-  // at most kRsCapBytes), d_rs_part the per-column pair sums of a group,
-  // d_rs_out dia and Λ of one state, the rest the operator of the call (CSR
-  // pattern, complex values per momentum, the direction's bond neighbours)
+  // holds rs_mats n2 x n2 matrices (W_k U of one group of vertices, at most
+  // kRsCapBytes, and for the current and operator responses the group's
+  // U^H W_k U behind them), d_rs_part the per-column Matsubara pair sums,
+  // d_rs_out one state's results, the rest the vertices of the call as one
+  // 2N-row CSR: d_rs_idx its rowptr (2N + 1), d_rs_col the columns, d_rs_val
+  // the complex values per vertex
   int64_t rs_mats = 0, rs_npart = 0, rs_nout = 0, rs_nval = 0, rs_ncol = 0, rs_nidx = 0;
   double2 *d_rs_ws = nullptr, *d_rs_val = nullptr;
   double *d_rs_part = nullptr, *d_rs_out = nullptr;
-  int *d_rs_col = nullptr, *d_rs_idx = nullptr;   // d_rs_idx: rowptr (N + 1), then nbr (3 N)
-  // operator response (dwh_measure_operator_response): shares the buffers
-  // above (d_rs_ws: Ṽ U and V_nm of one group of operators; d_rs_part; d_rs_out:
-  // χ then χ'' of one state; d_rs_val / d_rs_col / d_rs_idx: the 2N-row CSR of
-  // the call); d_op_part holds the χ'' partials of a group (operators x column
-  // chunks x frequencies), released with them
+  int *d_rs_col = nullptr, *d_rs_idx = nullptr;
+  // current response: the direction's bond neighbours (3 x N), for the
+  // diamagnetic weight
+  int64_t rs_nnbr = 0;
+  int* d_rs_nbr = nullptr;
+  // operator response: the χ'' partials of a group (operators x column
+  // chunks x frequencies)
   int64_t op_npart = 0;
   double* d_op_part = nullptr;
-  // Nambu cross response (dwh_measure_nambu_response): shares d_rs_ws (W U of
-  // one group of vertices), d_rs_part (the Matsubara pair sums), d_rs_out and
-  // the CSR buffers; d_nb_x keeps X^k = U^H W_k U of every vertex of the call
-  // (a pair needs both of its matrices), d_nb_part the chi2 partials of one
-  // batch of pairs, d_nb_pairs the pair list; released with the above
+  // Nambu cross response: d_nb_x keeps X^k = U^H W_k U of every vertex of the
+  // call (a pair needs both of its matrices), d_nb_part the chi2 partials of
+  // one batch of pairs, d_nb_pairs the pair list
   int64_t nb_nx = 0, nb_npart = 0, nb_npairs = 0;
   double2* d_nb_x = nullptr;
   double* d_nb_part = nullptr;
@@ -320,8 +323,13 @@ struct TrSrc {
   int64_t chain0;
   int cstep;
 };
+// dwhmc_eigsolve.cpp: the chains' own Δ from chain c0 on, the buffers of slot
+// k, the batched eigensolve of m slots (synchronises) and its rocSOLVER info
 TrSrc chains_src(const dwh_ctx* ctx, int64_t c0);
+TrBufs tr_slot(const dwh_ctx* ctx, int k);
 int eigen_solve(dwh_ctx* ctx, const TrSrc& src, int m);
 int eigen_info_check(dwh_ctx* ctx, int m);
+// dwhmc_measure.cpp: states per batched eigensolve of a _deltas / batched call
+int tr_group(const dwh_ctx* ctx, int64_t n);
 
 }  // namespace dwh

@@ -1,5 +1,6 @@
-// Device helpers shared by the dense Gauss-Jordan (dwhmc_kernels.hip) and the
-// block cyclic-reduction (dwhmc_cr.hip) kernels: complex arithmetic, the
+// Device helpers shared by the dense Gauss-Jordan (dwhmc_kernels.hip), the
+// block cyclic-reduction (dwhmc_cr.hip) and the measurement kernels: complex
+// arithmetic, the Fermi factors, the fixed-order block sum, the
 // XCD-aware grid remap, wave reductions, the wave-local 16x16 complex
 // inversion and the LDS-operand complex MFMA step (v_mfma_f64_16x16x4_f64).
 #pragma once
@@ -51,6 +52,35 @@ __device__ __forceinline__ double grid_point(double start, double step, int64_t 
 __device__ __forceinline__ double fermi_diff(double dE, double fn, double gn, double fm, double gm, double beta) {
   const double x = beta * dE;
   return x >= 0 ? -(fn * gm) * expm1(-x) : (fm * gn) * expm1(x);
+}
+// LogExpFunctions.logistic, overflow-safe (the Fermi factor f_n = logistic(-β E_n))
+__device__ inline double logistic_d(double x) {
+  if (x >= 0) return 1.0 / (1.0 + exp(-x));
+  const double e = exp(x);
+  return e / (1.0 + e);
+}
+// 1/p with v_rcp_f64 + one Newton step (<= ~11 ulp): the reciprocal of the
+// Lorentzian sums (k_tr_sigma, k_op_spec, k_nb_spec), a few ulp of the sum of
+// the terms' absolute values
+__device__ inline double rcp_nr1(double p) {
+  const double r = __builtin_amdgcn_rcp(p);
+  return fma(r, fma(-p, r, 1.0), r);
+}
+// fixed-order tree sum of NV values per thread over a block of TB threads (a
+// power of two); result in sh[v][0]
+template <int NV, int TB>
+__device__ inline void block_sum(double (&v)[NV], double (*sh)[TB]) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) sh[k][tid] = v[k];
+  __syncthreads();
+  for (int s = TB / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+#pragma unroll
+      for (int k = 0; k < NV; ++k) sh[k][tid] += sh[k][tid + s];
+    }
+    __syncthreads();
+  }
 }
 // 1/a with v_rcp_f64 + two Newton steps (error ~1 ulp; the IEEE division
 // sequence has ~3x the latency and sits on the pivot dependency chain).

@@ -34,7 +34,7 @@
 //     QR, twice (exact degeneracies of clean lattices included).  Every other pair is orthogonal only to
 //     ~eps ||T|| / gap <= ~2e-10 after inverse iteration; one symmetric
 //     (Löwdin) orthogonalisation step over all vectors (the library's real
-//     products, dwhmc_gemm.hip, driven by dwhmc_measure.cpp) takes those overlaps
+//     products, dwhmc_gemm.hip, driven by dwhmc_eigsolve.cpp) takes those overlaps
 //     to rounding.  (kEigZeroTol = 2.5e-4 ||T|| is a different tolerance: the
 //     particle-hole split point c0 below.)
 //     For H_BdG (the only matrices the library decomposes) steps 3-4 run on
@@ -998,7 +998,7 @@ __global__ __launch_bounds__(64) void k_eig_invit(const double* __restrict__ d, 
 // cluster the rotation is O(that) for distinct eigenvalues, and an orthonormal
 // basis of the eigenspace for exactly degenerate ones.  One workgroup per
 // candidate first index; clusters longer than maxc are left to the host-driven
-// Cholesky QR (long_clusters in dwhmc_measure.cpp); *bad = 1 when G is not
+// Cholesky QR (long_clusters in dwhmc_eigsolve.cpp); *bad = 1 when G is not
 // positive definite (the caller then re-solves with rocSOLVER's zheev).
 __global__ __launch_bounds__(256) void k_eig_orth(const double* __restrict__ E, const double* __restrict__ tnorm,
                                                   int n, double* __restrict__ Zt, int64_t sZ, double ctol,
@@ -1015,7 +1015,7 @@ __global__ __launch_bounds__(256) void k_eig_orth(const double* __restrict__ E, 
   while (end < n && end - j <= MC && E[end] - E[end - 1] <= tol) ++end;
   const int kc = end - j;
   // a cluster longer than maxc is orthonormalised by the host-driven Cholesky
-  // QR over several workgroups (own_heev_enqueue, dwhmc_measure.cpp)
+  // QR over several workgroups (own_heev_enqueue, dwhmc_eigsolve.cpp)
   if (kc == 1 || kc > maxc) return;
   constexpr int RC = 64;   // rows per LDS chunk (Gram sums, substitution)
   __shared__ double G[MC][MC + 1];

@@ -4,7 +4,7 @@
 //   * J_mn = U^H (J U)                [src/Observables.jl:334-335]
 //   * rho = (U f(E)) U^H              [eig path: ρ = U f(E) U† of compute_forces!]
 //   * the eigensolver's back-transform (W = V^H U, U -= V W2) and Löwdin step
-//     (G = Z Z^T, Y = 3/2 Y - 1/2 G Z), dwhmc_eig.hip / dwhmc_measure.cpp
+//     (G = Z Z^T, Y = 3/2 Y - 1/2 G Z), dwhmc_eig.hip / dwhmc_eigsolve.cpp
 // C = alpha op(A) op(B) + beta C, column-major, op in {N, C} (C: conjugate
 // transpose; transpose for real), complex (3 real MFMAs per complex MAC:
 // t1 = Ar Br, t2 = Ai Bi, t3 = (Ar + Ai)(Br + Bi); re = t1 - t2,

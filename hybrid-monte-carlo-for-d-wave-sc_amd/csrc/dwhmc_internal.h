@@ -1,5 +1,5 @@
 // Internal launch interface between the C-ABI context (dwhmc_api.cpp: steps,
-// creation, HMC; dwhmc_measure.cpp: eigensolver driver and transport;
+// creation, HMC; dwhmc_eigsolve.cpp: eigensolver driver; dwhmc_measure.cpp: measurements;
 // dwhmc_plan.cpp: the cyclic-reduction plan) and the gfx950 kernels
 // (dwhmc_*.hip).  Not part of the public ABI.
 #pragma once
@@ -10,6 +10,10 @@
 #include <type_traits>
 
 namespace dwh {
+
+constexpr double kTwoPi = 6.28318530717958647692;
+// blocks of b that cover a items
+inline int cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
 
 constexpr int kGJ = 64;        // Gauss-Jordan block (rows/cols of one diagonal block)
 constexpr int kSlots = 4;      // pairing entries per BdG row (NN bonds)
@@ -372,10 +376,7 @@ constexpr int kRsLChunk = 8;
 // bond list nbr (3 x N neighbours, 0-based) with hoppings tb[3] (host)
 void launch_rs_colstats(const double2* U, int N, const double* E, double beta, const double* tb, const int* nbr,
                         double* f, double* g, double* dia, hipStream_t s);
-// JU_q = (Jq ⊕ Jq) U, q < nq: Jq in CSR form (N rows, one pattern, nnz complex
-// values per q at val + q nnz), JU_q at JU + q sJU
-void launch_rs_current(const double2* U, double2* JU, int64_t sJU, int N, const int* rowptr, const int* col,
-                       const double2* val, int nnz, int nq, hipStream_t s);
+// (JU_q = (Jq ⊕ Jq) U: launch_op_apply on the 2N-row CSR of Jq ⊕ Jq)
 // part[(q nl + l) n2 + m] = Σ_n r_nm(l) |J_nm(q)|², l < nl, q < nq (J_nm(q) at Jnm + q sJ)
 void launch_rs_pairs(const double2* Jnm, int64_t sJ, int N, const double* E, const double* f, const double* g,
                      double beta, int nl, int nq, double* part, hipStream_t s);
@@ -386,7 +387,19 @@ void launch_rs_sum(const double* in, int cnt, int nout, double scale, double* ou
 // the operators in groups; the Matsubara sums are launch_rs_pairs / launch_rs_sum.
 // Most column chunks of the χ'' partials (one partial per chunk, ω and operator)
 constexpr int kOpSpecChunks = 512;
-int op_spec_chunks(int N);   // chunks in use at this N (rows of the partial buffer per operator, each nw long)
+// the column chunks of the χ'' partials at this N: columns per chunk and chunks
+// in use (every chunk non-empty; rows of the partial buffer per operator or
+// per pair and part, each nw long)
+inline void op_spec_split(int N, int* cols, int* used) {
+  const int n2 = 2 * N, nchunk = n2 < kOpSpecChunks ? n2 : kOpSpecChunks;
+  *cols = cdiv(n2, nchunk);
+  *used = cdiv(n2, *cols);
+}
+inline int op_spec_chunks(int N) {
+  int cols, used;
+  op_spec_split(N, &cols, &used);
+  return used;
+}
 // f_n = logistic(-β E_n), g_n = logistic(+β E_n), n < 2N
 void launch_op_fermi(const double* E, int N, double beta, double* f, double* g, hipStream_t s);
 // VU_k = Ṽ_k U, k < nops: Ṽ in CSR form (2N rows, columns < 2N, one pattern, nz
@@ -399,6 +412,12 @@ void launch_op_apply(const double2* U, double2* VU, int64_t sVU, int N, const in
 void launch_op_spec(const double2* Vnm, int64_t sV, int N, const double* E, const double* f, const double* g,
                     double beta, double eta, double w_start, double w_step, int nw, int nops, double* part,
                     double* out, hipStream_t s);
+
+// out = scale Σ_chunks part[(b nchunk + chunk) nw + j], b < nrows, j < nw, the
+// chunks in a fixed order; real rows: out[b nw + j]; complex_out (rows b = 2 p
+// + c, re / im of pair p): out[2 (p nw + j) + c]
+void launch_op_spec_sum(const double* part, int nchunk, int nw, int nrows, double scale, double* out,
+                        bool complex_out, hipStream_t s);
 
 // Cross response of general Nambu vertices (dwhmc_nambu.hip), one state at a
 // time: X^k = U^H W_k U at X + k sX for every vertex of the call, pairs as 2

@@ -15,7 +15,7 @@
 //                  block streams 256-row tiles (ΔE once, P complex weights) of a
 //                  column chunk through LDS; one reciprocal per (n, m, ω) serves
 //                  the 2P accumulators
-//   k_nb_spec_sum  the chunks added in a fixed order, times η/N
+//   (launch_op_spec_sum adds the chunks in a fixed order, times η/N)
 // All plain fp64 VALU, every sum in a fixed order (no atomics).  Matrices are
 // column-major with leading dimension n2 = 2N.
 #include "dwhmc_device.h"
@@ -25,24 +25,7 @@ namespace dwh {
 namespace {
 
 constexpr int kTB = 256;   // threads per block of every kernel here; rows per tile of k_nb_spec
-constexpr double kTwoPi = 6.28318530717958647692;
 constexpr int kNbW = 2;   // frequencies per thread of k_nb_spec
-
-// fixed-order tree sum of NV values per thread over the block; result in sh[v][0]
-template <int NV>
-__device__ inline void block_sum(double (&v)[NV], double (*sh)[kTB]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) sh[k][tid] = v[k];
-  __syncthreads();
-  for (int s = kTB / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-#pragma unroll
-      for (int k = 0; k < NV; ++k) sh[k][tid] += sh[k][tid + s];
-    }
-    __syncthreads();
-  }
-}
 
 // M = a conj(b)
 __device__ inline double2 mul_conj(double2 a, double2 b) {
@@ -98,12 +81,6 @@ k_nb_pairs(const double2* __restrict__ X, int64_t sX, int n2, const int* __restr
         part[(((size_t)p * nl + l0 + k) * 2 + 1) * n2 + m] = sh[2 * k + 1][0];
       }
   }
-}
-
-// v_rcp_f64 + one Newton step (<= ~11 ulp), as k_op_spec
-__device__ inline double rcp_nr1(double p) {
-  const double r = __builtin_amdgcn_rcp(p);
-  return fma(r, fma(-p, r, 1.0), r);
 }
 
 // chi2 partials of the P pairs p0 + z P + k, k < P, of block (x, y, z): a
@@ -206,29 +183,6 @@ k_nb_spec(const double2* __restrict__ X, int64_t sX, int n2, const int* __restri
   }
 }
 
-// out[2 (j + nw p) + c] = scale Σ_chunks part[((p 2 + c) nchunk + chunk) nw + j]
-// for blockIdx.y = p 2 + c (π·(1/π) cancels, scale = η/N): 64 ω per block, wave
-// q sums the chunks [q nchunk/4, (q+1) nchunk/4), the four in wave order
-__global__ void k_nb_spec_sum(const double* __restrict__ part, int nchunk, int nw, double scale,
-                              double* __restrict__ out) {
-  __shared__ double sh[4][64];
-  const int l = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const int j = blockIdx.x * 64 + l;
-  const double* p = part + (size_t)blockIdx.y * nchunk * nw;
-  double s = 0;
-  if (j < nw) {
-    const int c0 = nchunk * q / 4, c1 = nchunk * (q + 1) / 4;
-    for (int c = c0; c < c1; ++c) s += p[(size_t)c * nw + j];
-  }
-  sh[q][l] = s;
-  __syncthreads();
-  if (q == 0 && j < nw)
-    out[2 * ((size_t)(blockIdx.y >> 1) * nw + j) + (blockIdx.y & 1)] =
-        (((sh[0][l] + sh[1][l]) + sh[2][l]) + sh[3][l]) * scale;
-}
-
-inline int cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
-
 template <int P>
 void spec_group(dim3 grid, hipStream_t s, const double2* X, int64_t sX, int n2, const int* pr, int p0,
                 const double* E, const double* f, const double* g, double beta, double eta, double w_start,
@@ -256,8 +210,9 @@ void launch_nb_spec(const double2* X, int64_t sX, int N, const int* pairs, int p
                     const double* f, const double* g, double beta, double eta, double w_start, double w_step, int nw,
                     double* part, double* out, hipStream_t s) {
   if (npairs <= 0 || nw <= 0) return;
-  const int n2 = 2 * N, nchunk = std::min(n2, kOpSpecChunks);
-  const int cols = cdiv(n2, nchunk), used = cdiv(n2, cols);
+  const int n2 = 2 * N;
+  int cols, used;
+  op_spec_split(N, &cols, &used);
   const int full = npairs / kNbSpecGroup, rem = npairs % kNbSpecGroup;
   const int nx = cdiv(nw, kNbW * kTB);
   // the groups of kNbSpecGroup pairs, then the last, partial one on the
@@ -272,8 +227,8 @@ void launch_nb_spec(const double2* X, int64_t sX, int N, const int* pairs, int p
   if (rem == 2) spec_group<2>(gt, s, X, sX, n2, pairs, pt, E, f, g, beta, eta, w_start, w_step, nw, cols, tail);
   if (rem == 3) spec_group<3>(gt, s, X, sX, n2, pairs, pt, E, f, g, beta, eta, w_start, w_step, nw, cols, tail);
   static_assert(kNbSpecGroup == 4, "the tail dispatch covers group sizes 1 .. 3");
-  hipLaunchKernelGGL(k_nb_spec_sum, dim3(cdiv(nw, 64), 2 * npairs), dim3(256), 0, s, part, used, nw, eta / N,
-                     out + 2 * (size_t)p0 * nw);
+  // out[2 (j + nw p) + c] from the rows p 2 + c of the partials
+  launch_op_spec_sum(part, used, nw, 2 * npairs, eta / N, out + 2 * (size_t)p0 * nw, true, s);
 }
 
 }  // namespace dwh

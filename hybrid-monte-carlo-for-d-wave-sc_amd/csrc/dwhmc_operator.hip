@@ -16,7 +16,8 @@
 //                  256-pair tiles (ΔE_nm, c_nm) of a chunk of columns m through
 //                  LDS; no (n, m) <-> (m, n) fold (χ''(ω) is not odd in ω for a
 //                  non-Hermitian V), ω of either sign, no 1/ω
-//   k_op_spec_sum  the chunks added in a fixed order, times η/N
+//   k_op_spec_sum  the chunks added in a fixed order, times η/N (real rows here,
+//                  the re / im rows of dwhmc_nambu.hip's pairs interleaved)
 // All plain fp64 VALU, every sum in a fixed order (no atomics).  Matrices are
 // column-major with leading dimension n2 = 2N, as in dwhmc_transport.hip.
 #include "dwhmc_device.h"
@@ -26,13 +27,6 @@ namespace dwh {
 namespace {
 
 constexpr int kTB = 256;   // threads per block of every kernel here; pairs per tile of k_op_spec
-
-// LogExpFunctions.logistic, overflow-safe (as dwhmc_response.hip's)
-__device__ inline double logistic_d(double x) {
-  if (x >= 0) return 1.0 / (1.0 + exp(-x));
-  const double e = exp(x);
-  return e / (1.0 + e);
-}
 
 __global__ void k_op_fermi(const double* __restrict__ E, int n2, double beta, double* __restrict__ f,
                            double* __restrict__ g) {
@@ -45,9 +39,10 @@ __global__ void k_op_fermi(const double* __restrict__ E, int n2, double beta, do
 // VU_k = Ṽ_k U for the operators k of a group (blockIdx.z): Ṽ in CSR form with
 // n2 rows (rows < N: V, columns < N; rows >= N: -s V^T, columns >= N; one
 // pattern for every k, duplicates summed on the host), complex values
-// val[k nz + e]; VU_k at VU + k sVU.  Column n of U per blockIdx.y.  The
-// layout and grid of k_rs_current; a row >= N reads its own CSR row, whose
-// columns point into the hole half of the column.
+// val[k nz + e]; VU_k at VU + k sVU.  Column n of U per blockIdx.y.  A row
+// >= N reads its own CSR row, whose columns point into the hole half of the
+// column.  The current response's Jq ⊕ Jq and the Nambu vertices come in the
+// same form.
 __global__ void k_op_apply(const double2* __restrict__ U, double2* __restrict__ VU, int64_t sVU, int n2,
                            const int* __restrict__ rowptr, const int* __restrict__ col,
                            const double2* __restrict__ val, int nz) {
@@ -63,14 +58,6 @@ __global__ void k_op_apply(const double2* __restrict__ U, double2* __restrict__ 
     acc.y += v.x * b.y + v.y * b.x;
   }
   VU[(size_t)k * sVU + (size_t)n * n2 + r] = acc;
-}
-
-// v_rcp_f64 + one Newton step (<= ~11 ulp), as k_tr_sigma.  The χ'' terms
-// carry both signs, so the error bound is relative to Σ |c_nm| / ((ω - ΔE)² +
-// η²), not to χ'' itself: a few ulp of the absolute sum.
-__device__ inline double rcp_nr1(double p) {
-  const double r = __builtin_amdgcn_rcp(p);
-  return fma(r, fma(-p, r, 1.0), r);
 }
 
 // χ'' partials.  Block (x, y, z): ω_j for j in the x tile, columns m in
@@ -127,9 +114,12 @@ k_op_spec(const double2* __restrict__ Vnm, int64_t sV, int n2, const double* __r
   if (j < nw) part[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * nw + j] = acc0 + acc1;
 }
 
-// χ''(ω_j) of operator blockIdx.y = η/N Σ_chunks part (π·(1/π) cancels): 64 ω
-// per block, wave q sums the chunks [q nchunk/4, (q+1) nchunk/4), the four in
-// wave order
+// Row blockIdx.y of the partials summed over its chunks, times scale = η/N
+// (π·(1/π) cancels): 64 ω per block, wave q sums the chunks [q nchunk/4,
+// (q+1) nchunk/4), the four in wave order.  Real rows (χ''(ω_j) of operator
+// blockIdx.y): out[blockIdx.y nw + j]; COMPLEX_OUT (row 2 p + c = re / im of
+// pair p): out[2 (p nw + j) + c]
+template <bool COMPLEX_OUT>
 __global__ void k_op_spec_sum(const double* __restrict__ part, int nchunk, int nw, double scale,
                               double* __restrict__ out) {
   __shared__ double sh[4][64];
@@ -143,26 +133,14 @@ __global__ void k_op_spec_sum(const double* __restrict__ part, int nchunk, int n
   }
   sh[q][l] = s;
   __syncthreads();
-  if (q == 0 && j < nw)
-    out[(size_t)blockIdx.y * nw + j] = (((sh[0][l] + sh[1][l]) + sh[2][l]) + sh[3][l]) * scale;
-}
-
-inline int cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
-
-// columns per chunk and chunks in use (every chunk non-empty)
-inline void spec_split(int N, int* cols, int* used) {
-  const int n2 = 2 * N, nchunk = std::min(n2, kOpSpecChunks);
-  *cols = cdiv(n2, nchunk);
-  *used = cdiv(n2, *cols);
+  if (q == 0 && j < nw) {
+    const size_t o = COMPLEX_OUT ? 2 * ((size_t)(blockIdx.y >> 1) * nw + j) + (blockIdx.y & 1)
+                                 : (size_t)blockIdx.y * nw + j;
+    out[o] = (((sh[0][l] + sh[1][l]) + sh[2][l]) + sh[3][l]) * scale;
+  }
 }
 
 }  // namespace
-
-int op_spec_chunks(int N) {
-  int cols, used;
-  spec_split(N, &cols, &used);
-  return used;
-}
 
 void launch_op_fermi(const double* E, int N, double beta, double* f, double* g, hipStream_t s) {
   hipLaunchKernelGGL(k_op_fermi, dim3(cdiv(2 * N, kTB)), dim3(kTB), 0, s, E, 2 * N, beta, f, g);
@@ -180,10 +158,17 @@ void launch_op_spec(const double2* Vnm, int64_t sV, int N, const double* E, cons
                     double* out, hipStream_t s) {
   if (nops <= 0 || nw <= 0) return;
   int cols, used;
-  spec_split(N, &cols, &used);
+  op_spec_split(N, &cols, &used);
   hipLaunchKernelGGL(k_op_spec, dim3(cdiv(nw, kTB), used, nops), dim3(kTB), 0, s, Vnm, sV, 2 * N, E, f, g, beta, eta,
                      w_start, w_step, nw, cols, part);
-  hipLaunchKernelGGL(k_op_spec_sum, dim3(cdiv(nw, 64), nops), dim3(256), 0, s, part, used, nw, eta / N, out);
+  launch_op_spec_sum(part, used, nw, nops, eta / N, out, false, s);
+}
+
+void launch_op_spec_sum(const double* part, int nchunk, int nw, int nrows, double scale, double* out,
+                        bool complex_out, hipStream_t s) {
+  const dim3 grid(cdiv(nw, 64), nrows);
+  if (complex_out) hipLaunchKernelGGL(k_op_spec_sum<true>, grid, dim3(256), 0, s, part, nchunk, nw, scale, out);
+  else hipLaunchKernelGGL(k_op_spec_sum<false>, grid, dim3(256), 0, s, part, nchunk, nw, scale, out);
 }
 
 }  // namespace dwh

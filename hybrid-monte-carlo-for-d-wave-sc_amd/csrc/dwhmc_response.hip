@@ -5,8 +5,9 @@
 //
 // From the eigenpairs E, U of one state, driven by dwhmc_measure.cpp:
 //   k_rs_colstats  f_n and the diamagnetic weight of direction α per eigenstate
-//   k_rs_current   JU_q = (Jq ⊕ Jq) U for a group of momenta (one launch)
-//   (J_nm(q) = U^H JU_q: the library's own batched product, U shared at stride 0)
+//   (JU_q = (Jq ⊕ Jq) U for a group of momenta: dwhmc_operator.hip's k_op_apply
+//    on the 2N-row CSR of Jq ⊕ Jq; J_nm(q) = U^H JU_q: the library's own batched
+//    product, U^H shared at stride 0)
 //   k_rs_pairs     per column m of J_nm(q): Σ_n r_nm(l) |J_nm|² for a chunk of l
 //   k_rs_sum       the columns (and the eigenstates of dia) added in a fixed order
 // All plain fp64 VALU; every sum has a fixed order (no atomics), so results
@@ -19,30 +20,6 @@ namespace dwh {
 namespace {
 
 constexpr int kTB = 256;   // threads per block of every kernel here
-constexpr double kTwoPi = 6.28318530717958647692;
-
-// LogExpFunctions.logistic, overflow-safe (f_n = logistic(-β E_n))
-__device__ inline double logistic_d(double x) {
-  if (x >= 0) return 1.0 / (1.0 + exp(-x));
-  const double e = exp(x);
-  return e / (1.0 + e);
-}
-
-// fixed-order tree sum of NV values per thread over the block; result in sh[v][0]
-template <int NV>
-__device__ inline void block_sum(double (&v)[NV], double (*sh)[kTB]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) sh[k][tid] = v[k];
-  __syncthreads();
-  for (int s = kTB / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-#pragma unroll
-      for (int k = 0; k < NV; ++k) sh[k][tid] += sh[k][tid + s];
-    }
-    __syncthreads();
-  }
-}
 
 // Per eigenstate n (one block per column of U): f_n = logistic(-β E_n),
 // g_n = 1 - f_n = logistic(+β E_n) (its own exponential: no cancellation) and
@@ -77,27 +54,6 @@ __global__ void k_rs_colstats(const double2* __restrict__ U, int n2, int N, cons
     g[n] = logistic_d(beta * e);
     dia[n] = e > 0 ? sh[0][0] * tanh(0.5 * beta * e) : 0.0;
   }
-}
-
-// JU_q = (Jq ⊕ Jq) U for the momenta q of a group (blockIdx.z): Jq in CSR form
-// (N rows; one pattern for every q, duplicates summed on the host), complex
-// values val[q nnz + k]; JU_q at JU + q sJU.  Column n of U per blockIdx.y.
-__global__ void k_rs_current(const double2* __restrict__ U, double2* __restrict__ JU, int64_t sJU, int n2, int N,
-                             const int* __restrict__ rowptr, const int* __restrict__ col,
-                             const double2* __restrict__ val, int nnz) {
-  const int r = blockIdx.x * kTB + threadIdx.x;
-  if (r >= n2) return;
-  const int n = blockIdx.y, q = blockIdx.z;
-  const int rr = r < N ? r : r - N, off = r < N ? 0 : N;
-  const double2* u = U + (size_t)n * n2 + off;
-  const double2* a = val + (size_t)q * nnz;
-  double2 acc = make_double2(0.0, 0.0);
-  for (int k = rowptr[rr]; k < rowptr[rr + 1]; ++k) {
-    const double2 j = a[k], b = u[col[k]];
-    acc.x += j.x * b.x - j.y * b.y;
-    acc.y += j.x * b.y + j.y * b.x;
-  }
-  JU[(size_t)q * sJU + (size_t)n * n2 + r] = acc;
 }
 
 // Per column m of J_nm(q) (threads over n; blockIdx.y = q of the group): for
@@ -154,21 +110,12 @@ __global__ void k_rs_sum(const double* __restrict__ in, int cnt, double scale, d
   if (threadIdx.x == 0) out[blockIdx.x] = scale * sh[0][0];
 }
 
-inline int cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
-
 }  // namespace
 
 void launch_rs_colstats(const double2* U, int N, const double* E, double beta, const double* tb, const int* nbr,
                         double* f, double* g, double* dia, hipStream_t s) {
   hipLaunchKernelGGL(k_rs_colstats, dim3(2 * N), dim3(kTB), 0, s, U, 2 * N, N, E, beta, tb[0], tb[1], tb[2], nbr, f,
                      g, dia);
-}
-
-void launch_rs_current(const double2* U, double2* JU, int64_t sJU, int N, const int* rowptr, const int* col,
-                       const double2* val, int nnz, int nq, hipStream_t s) {
-  if (nq <= 0) return;
-  hipLaunchKernelGGL(k_rs_current, dim3(cdiv(2 * N, kTB), 2 * N, nq), dim3(kTB), 0, s, U, JU, sJU, 2 * N, N, rowptr,
-                     col, val, nnz);
 }
 
 void launch_rs_pairs(const double2* Jnm, int64_t sJ, int N, const double* E, const double* f, const double* g,

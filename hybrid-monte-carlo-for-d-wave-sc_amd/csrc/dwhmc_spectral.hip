@@ -33,8 +33,6 @@ constexpr int kTB = 256;
 constexpr double kInvPi = 0.31830988618379067154;
 constexpr int kMaxDft = 1024;   // longest lattice side with its twiddles in LDS (as k_tr_dft_x)
 
-inline int cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
-
 // Λ[n, q] = L(ω_q - E_n) at Lam[q + ldq n] for q < cnt, n < n2; ω_q = point
 // first + q stride of the grid d0 + k dw; state s = blockIdx.z
 __global__ void __launch_bounds__(kTB)

@@ -5,8 +5,8 @@
 // sweeps (src/Simulation.jl:170-186), not the leapfrog hot path: the
 // eigenpairs come from the library's own Hermitian eigensolver
 // (dwhmc_eig.hip) and J_mn = U^H (J ⊕ J) U from its own batched fp64 MFMA
-// product (dwhmc_gemm.hip), both driven by dwhmc_measure.cpp; the kernels here
-// are everything around them.  All matrices are column-major with leading dimension n2 = 2N (the
+// product (dwhmc_gemm.hip), driven by dwhmc_eigsolve.cpp and
+// dwhmc_measure.cpp; the kernels here are everything around them.  All matrices are column-major with leading dimension n2 = 2N (the
 // eigenvector of E_n is column n of U, as Julia's eigen! returns it).
 //
 // The O(n2^2 · n_ω) optical-conductivity sum is the only heavy kernel: every
@@ -23,29 +23,6 @@ namespace {
 constexpr int kTB = 256;   // threads per block of every kernel here
 constexpr double kInvPi = 0.31830988618379067154;
 constexpr int kMaxDft = 1024;   // longest lattice side of the A(k, 0) DFT passes (twiddle table in LDS)
-
-// LogExpFunctions.logistic, overflow-safe (the fermi factor f_n = logistic(-βE_n))
-__device__ inline double logistic_d(double x) {
-  if (x >= 0) return 1.0 / (1.0 + exp(-x));
-  const double e = exp(x);
-  return e / (1.0 + e);
-}
-
-// fixed-order tree sum of NV values per thread over the block; result in sh[v][0]
-template <int NV>
-__device__ inline void block_sum(double (&v)[NV], double (*sh)[kTB]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) sh[k][tid] = v[k];
-  __syncthreads();
-  for (int s = kTB / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-#pragma unroll
-      for (int k = 0; k < NV; ++k) sh[k][tid] += sh[k][tid + s];
-    }
-    __syncthreads();
-  }
-}
 
 // Dense H_BdG = [[h, D], [conj(D), -h]] of one chain (init_static_H! +
 // update_H_BdG!, src/Hamiltonian.jl:10-86); hcol/hval hold h with the
@@ -184,14 +161,9 @@ __global__ void k_tr_pairs(const double2* __restrict__ Jmn, int n2, const double
 // of the Fermi level; a 256-pair tile whose c are all zero is skipped.
 // Block (x, y): ω_k for k in the x tile, rows n in [y·rows, (y+1)·rows),
 // m > n read down column n of J_mn (|J_nm| = |J_mn|, J_mn Hermitian).
-// one Newton step (<= ~11 ulp, the bisection's Sturm count uses the same): the
+// rcp_nr1 (dwhmc_device.h; the bisection's Sturm count uses the same): the
 // σ terms are positive-weighted sums, so a few-ulp relative error per term
-// is a few-ulp relative error of σ
-__device__ inline double rcp_nr1(double p) {
-  const double r = __builtin_amdgcn_rcp(p);
-  return fma(r, fma(-p, r, 1.0), r);
-}
-
+// is a few-ulp relative error of σ.
 // ph (launch_tr_reduce): rows n < N only, m in (n, n2-1-n], the pairs
 // strictly inside counted twice (each stands for its particle-hole partner
 // (n2-1-m, n2-1-n)), the self-partnered m = n2-1-n once.
@@ -481,8 +453,6 @@ __global__ void k_nonfinite(const double2* __restrict__ U, int64_t nu, const dou
   for (int64_t k = (int64_t)blockIdx.x * kTB + threadIdx.x; k < ne; k += stride) nf |= !isfinite(E[k]);
   if (nf) *bad = 1;
 }
-
-inline int cdiv(int64_t a, int b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
 

@@ -362,6 +362,14 @@ int dwh_measure_spectral_maps(dwh_ctx* ctx, int64_t chain, int64_t nstates, cons
 int dwh_measure_current_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta,
                                  int32_t direction, int64_t nq, const int64_t* q, int64_t n_matsubara,
                                  double* dia, double* lambda);
+/* Host only (no device, no context): the vertices the call above uploads for
+ * the lattice (Lx, Ly, t, tp and the 1-based neighbour tables of dwh_create),
+ * Jq ⊕ Jq on one 2N-row CSR with duplicates summed, expanded to dense: out
+ * holds nq matrices, 2N x 2N column-major.  DWH_ERR_ARG as above and for the
+ * lattice as dwh_create, the text where dwh_last_error(NULL) reads it. */
+int dwh_debug_current_vertex(int64_t Lx, int64_t Ly, double t, double tp, const int64_t* nn_table,
+                             const int64_t* nnn_table, int32_t direction, int64_t nq, const int64_t* q,
+                             dwh_c128* out);
 /* Bench (tools/bench_current_response.py): the product of one momentum alone,
  * (2N x 2N)·(2N x 2N) 'N','N' on the measurement buffers of slot 0 as the last
  * measurement left them, reps times back to back after one warm-up launch,

@@ -84,7 +84,7 @@ def _q_crowd(E, j0, tn):
 
 
 def _q_accepts(E, tn):
-    """q_heev_enqueue's host decision (csrc/dwhmc_measure.cpp)."""
+    """q_heev_enqueue's host decision (csrc/dwhmc_eigsolve.cpp)."""
     n = len(E)
     j0 = n // 2
     crowd = _q_crowd(E, j0, tn)

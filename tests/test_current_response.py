@@ -17,7 +17,8 @@ transport tolerance |Δ| <= 1e-9 (1 + |ref|) (tests/test_transport.py header);
 every sum is basis-invariant inside degenerate levels.
 
 CPU (not gpu): the restatement against the oracle's stiffness, its ±q and x<->y
-identities, the clean 8 x 8 values, the NULL-context refusal and the driver
+identities, the clean 8 x 8 values, the NULL-context refusal, the vertices the
+library uploads (dwh_debug_current_vertex) against the triplet sum and the driver
 option on the oracle backend.  GPU: parity on lattices below / at / above the
 product tile with tails and on the Lx = 2 ring, the grouping loop, consistency
 with measure_transport, ±q, degenerate spectra with both solvers, snapshots,
@@ -190,6 +191,28 @@ def test_null_context_is_refused(dwhmc):
     assert lib.dwh_measure_current_response(None, 0, 1, None, 0, 1, pq, 1, pb, pb) == -1
     assert b"NULL" in lib.dwh_last_error(None)
     assert dwhmc.FermionContext.TIMERS.index("response") == 13
+
+
+@pytest.mark.parametrize("a", ["x", "y"])
+@pytest.mark.parametrize("Lx,Ly", [(4, 4), (5, 7), (2, 4)])
+def test_debug_current_vertex(dwhmc, oracle, Lx, Ly, a):
+    """The vertices the library uploads (dwh_debug_current_vertex, host only)
+    are Jq ⊕ Jq of the triplet sum.  At Lx = 2 the +x and -x neighbours
+    coincide: the duplicates' sum and the transposed entry share a slot."""
+    p = oracle.ModelParameters(Lx, Ly, T, TP, MU, 0.0, 0.0, 8.0, 0.8, 1.0)
+    N = p.N
+    qs = [(0, 0), (1, 0), (0, 1), (-1, 2), (Lx, Ly)]
+    got = dwhmc.debug_current_vertex(p.Lx, p.Ly, p.t, p.tp, p.nn_table, p.nnn_table, a, qs)
+    assert got.shape == (len(qs), 2 * N, 2 * N)
+    for k, (mx, my) in enumerate(qs):
+        J = _jq(p, a, mx, my)
+        err = max(np.abs(got[k, :N, :N] - J).max(), np.abs(got[k, N:, N:] - J).max())
+        print("vertex", Lx, Ly, a, (mx, my), float(err))
+        for blk in (got[k, :N, :N], got[k, N:, N:]):
+            _close(blk.real, J.real, (a, mx, my, "re"))
+            _close(blk.imag, J.imag, (a, mx, my, "im"))
+        assert not got[k, :N, N:].any() and not got[k, N:, :N].any()
+    assert np.abs(got).max() > 0.1                          # (Lx = 2, x, q = 0 alone cancels to zero)
 
 
 class _OracleResponse(OracleContext):
