@@ -6,7 +6,9 @@ Layout:
   context.py FermionContext: batched device handle
   hmc.py     the reference's hot-path API (ModelParameters ... hmc_sweep)
   vertices.py sparse one-body vertices for measure_operator_response and Nambu
-              vertices for measure_nambu_response (host numpy)
+              vertices for measure_nambu_response; site / bond patterns, the
+              contraction and the local stiffness maps for measure_response_map
+              (host numpy)
   simulation.py run_simulation (src/Simulation.jl): adaptive Nt, log, observables.csv
   replicas.py one-process-per-GPU replica driver (RCCL only gathers observables)
 

@@ -101,6 +101,10 @@ SIGNATURES = {
     "dwh_measure_nambu_response": (C.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _D, _D,
                                              _D, _I64, _P]),
     "dwh_debug_nambu_dense": (C.c_int, [_I64, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
+    "dwh_measure_response_map": (C.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _P, _I64, _D, _I64,
+                                           _P, _P, _P]),
+    "dwh_debug_response_map_plan": (C.c_int, [_I64, _I64, _P, _P, _P, _P]),
+    "dwh_bench_response_map_stages": (C.c_int, [_P, _I64, _I64, _DP, _DP]),
     "dwh_debug_dense_H": (C.c_int, [_P, _I64, _P]),
     "dwh_debug_qeig": (C.c_int, [_P, _I64, _P, _P]),
     "dwh_debug_set_eigensystem": (C.c_int, [_P, _I64, _P, _P, _I32]),

@@ -415,22 +415,7 @@ class FermionContext:
         npairs, n_w), omega (n_w,) and pairs (npairs, 2)."""
         from . import vertices as vx
         N = self.N
-        if isinstance(vertices, (vx.NambuVertex, vx.Vertex)):
-            vertices = [vertices]                                  # one vertex passed bare
-        # a CSR tuple is told by its content: an integer rowptr of 2N + 1 entries first
-        first = vertices[0] if isinstance(vertices, tuple) and len(vertices) == 3 else None
-        if first is not None and not isinstance(first, (tuple, list)) and np.ndim(first) == 1 \
-                and len(first) == 2 * N + 1 and np.issubdtype(np.asarray(first).dtype, np.integer):
-            rowptr = np.ascontiguousarray(vertices[0], dtype=np.int64).ravel()
-            col = np.ascontiguousarray(vertices[1], dtype=np.int64).ravel()
-            val = np.ascontiguousarray(np.atleast_2d(np.asarray(vertices[2], dtype=np.complex128)))
-            if val.ndim != 2 or val.shape[1] != len(col):
-                raise ValueError(f"vertices: a CSR tuple needs val (nops, {len(col)})")
-        else:
-            vertices = list(vertices)
-            if not vertices:
-                raise ValueError("vertices is empty")
-            rowptr, col, val = vx.union_csr_nambu(vertices, N)
+        rowptr, col, val = _nambu_csr(vx, vertices, N)
         nops, nnz = val.shape
         if pairs is None:
             pr = np.stack([np.arange(nops, dtype=np.int64)] * 2, axis=1)
@@ -467,6 +452,53 @@ class FermionContext:
         if deltas is None:
             return dict(chi=chi[0], chi2=chi2[0], omega=grid, pairs=pr)
         return dict(chi=chi, chi2=chi2, omega=grid, pairs=pr)
+
+    def measure_response_map(self, vertices, pattern, n_matsubara: int = 1, omega=None, eta=None, rho: bool = True,
+                             chain: int = 0, deltas=None) -> dict:
+        """Response maps (dwh_measure_response_map): the linear-response
+        density matrix D(z)[W] = U (w(z) ∘ U^H W U) U^H of each source vertex
+        W and the equal-time ρ = U f U^H, at the entries of a sparse pattern.
+        vertices: as measure_nambu_response takes them.  pattern: an (npat, 2)
+        integer array of Nambu index pairs (a, b) in [0, 2N), any order,
+        duplicates allowed (vertices.bond_pattern builds the site / bond
+        ones).  z runs over the n_matsubara Matsubara indices (the weights of
+        measure_nambu_response's chi) and then the real frequencies omega (a
+        list of either sign, w = (f_n - f_m)/(ΔE - ω - iη), needs eta > 0).
+        No 1/N is applied: vertices.contract(pattern, D, B) = N·chi of the
+        pair (W, B).  n_matsubara = 0 and omega None skips dmap, rho=False
+        skips ρ.  Returns dmap ((nstates,) nops, nz, npat) or None, rho
+        ((nstates,) npat) or None, pattern (npat, 2) and omega (n_w,)."""
+        from . import vertices as vx
+        N = self.N
+        rowptr, col, val = _nambu_csr(vx, vertices, N)
+        nops, nnz = val.shape
+        pat = np.asarray(pattern)
+        if pat.ndim != 2 or pat.shape[1] != 2 or not np.issubdtype(pat.dtype, np.integer):
+            raise ValueError("pattern: an (npat, 2) integer array of Nambu index pairs")
+        pat = np.ascontiguousarray(pat, dtype=np.int64)
+        prow, pcol = np.ascontiguousarray(pat[:, 0]), np.ascontiguousarray(pat[:, 1])
+        npat = pat.shape[0]
+        nl = int(n_matsubara)
+        w = np.zeros(0) if omega is None else np.ascontiguousarray(np.asarray(omega, dtype=np.float64).ravel())
+        nw = len(w)
+        if nw > 0 and eta is None:
+            raise ValueError("eta is needed with omega")
+        nz = max(nl, 0) + nw
+        D, ns = None, 1
+        if deltas is not None:
+            Dl = np.asarray(deltas, dtype=np.complex128)
+            if Dl.ndim != 3 or Dl.shape[1:] != (N, 2) or Dl.shape[0] < 1:
+                raise ValueError(f"expected (nstates, {N}, 2) pairing fields")
+            ns = Dl.shape[0]
+            D = np.ascontiguousarray(np.transpose(Dl, (0, 2, 1)))
+        dmap = np.empty((ns, nops, nz, npat), dtype=np.complex128) if nz > 0 else None
+        r = np.empty((ns, npat), dtype=np.complex128) if rho else None
+        self._c(self._lib.dwh_measure_response_map(
+            self._h, int(chain), ns, ptr(D), nops, ptr(rowptr), ptr(col), nnz, ptr(val), npat, ptr(prow), ptr(pcol),
+            nl, 0.0 if eta is None else float(eta), nw, ptr(w) if nw > 0 else None, ptr(r), ptr(dmap)))
+        if deltas is None:
+            dmap, r = (None if dmap is None else dmap[0]), (None if r is None else r[0])
+        return dict(dmap=dmap, rho=r, pattern=pat, omega=w)
 
     # -- assembly read-back (parity tests) --------------------------------
     def debug_dense_H(self, chain: int = 0) -> np.ndarray:
@@ -522,7 +554,7 @@ class FermionContext:
     # -- timing ----------------------------------------------------------
     TIMERS =("gj_update", "gj_pivot", "assemble", "contract", "step", "gj_edge", "cr_gemm", "cr_inv",
               "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral", "response", "operator",
-              "nambu")
+              "nambu", "map")
 
     def timing_enable(self, on=True):
         """on: True (all timers), False, or an iterable of timer names."""
@@ -548,12 +580,41 @@ class FermionContext:
         self._c(self._lib.dwh_bench_response_product(self._h, int(reps), C.byref(ms)))
         return ms.value
 
+    def bench_response_map_stages(self, reps: int, nfreq: int = 1):
+        """dwh_bench_response_map_stages: (weight_ms, sample_ms) per launch of
+        the weight kernel and of the sampled product for nfreq frequencies, on
+        the buffers of the last measure_response_map call with a dmap."""
+        tw, ts = C.c_double(), C.c_double()
+        self._c(self._lib.dwh_bench_response_map_stages(self._h, int(reps), int(nfreq), C.byref(tw), C.byref(ts)))
+        return tw.value, ts.value
+
     def timing_read(self, name: str):
         ms = C.c_double()
         n = C.c_int64()
         w = C.c_double()
         self._c(self._lib.dwh_timing_read(self._h, name.encode(), C.byref(ms), C.byref(n), C.byref(w)))
         return ms.value, n.value, w.value
+
+
+def _nambu_csr(vx, vertices, N: int):
+    """(rowptr, col, val (nops, nnz)) of the Nambu vertices of a call: a CSR
+    tuple as given, else a collection (or one bare vertex) on its union pattern."""
+    if isinstance(vertices, (vx.NambuVertex, vx.Vertex)):
+        vertices = [vertices]                                  # one vertex passed bare
+    # a CSR tuple is told by its content: an integer rowptr of 2N + 1 entries first
+    first = vertices[0] if isinstance(vertices, tuple) and len(vertices) == 3 else None
+    if first is not None and not isinstance(first, (tuple, list)) and np.ndim(first) == 1 \
+            and len(first) == 2 * N + 1 and np.issubdtype(np.asarray(first).dtype, np.integer):
+        rowptr = np.ascontiguousarray(vertices[0], dtype=np.int64).ravel()
+        col = np.ascontiguousarray(vertices[1], dtype=np.int64).ravel()
+        val = np.ascontiguousarray(np.atleast_2d(np.asarray(vertices[2], dtype=np.complex128)))
+        if val.ndim != 2 or val.shape[1] != len(col):
+            raise ValueError(f"vertices: a CSR tuple needs val (nops, {len(col)})")
+        return rowptr, col, val
+    vertices = list(vertices)
+    if not vertices:
+        raise ValueError("vertices is empty")
+    return vx.union_csr_nambu(vertices, N)
 
 
 def transport_grid(eta: float, domega: float, omega_max: float, lib=None):

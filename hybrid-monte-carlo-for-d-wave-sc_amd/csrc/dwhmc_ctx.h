@@ -23,7 +23,7 @@ namespace dwh {
 
 enum TimerName {
   T_GJ_UPDATE = 0, T_GJ_PIVOT, T_ASSEMBLE, T_CONTRACT, T_STEP, T_GJ_EDGE, T_CR_GEMM, T_CR_INV, T_CR_INVSIDE,
-  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_OPERATOR, T_NAMBU, T_COUNT
+  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_OPERATOR, T_NAMBU, T_MAP, T_COUNT
 };
 inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assemble", "contract",
                                                  "step",      "gj_edge",  "cr_gemm",  "cr_inv",
@@ -33,7 +33,8 @@ inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assem
                                                  "spectral",    // LDOS / A(k, ω) map stage (work: flops)
                                                  "response",    // Λ(q, iΩ) after its eigensolve (work: flops)
                                                  "operator",    // χ(iΩ), χ''(ω) of sparse vertices after their eigensolve (work: flops)
-                                                 "nambu"};      // cross response of Nambu vertices after its eigensolve (work: flops)
+                                                 "nambu",       // cross response of Nambu vertices after its eigensolve (work: flops)
+                                                 "map"};        // response maps after their eigensolve (work: flops)
 
 enum Algo { ALGO_DENSE = 0, ALGO_CR = 1, ALGO_EIG = 2 };
 
@@ -171,6 +172,19 @@ struct dwh_ctx {
   double2* d_nb_x = nullptr;
   double* d_nb_part = nullptr;
   int* d_nb_pairs = nullptr;
+  // response maps: d_map_ws holds the weighted matrices K_z and the products
+  // S_z = K_z U^H of one chunk of frequencies (2 x chunk n2 x n2 matrices, at
+  // most kRsCapBytes; one frequency is always allowed), d_map_out the chunk's
+  // sampled entries, d_map_omega the real frequencies, d_map_idx the
+  // column-grouped pattern (rows a and original indices, npat each) and
+  // d_map_slice its workgroup slices (3 ints each)
+  int64_t map_nws = 0, map_nout = 0, map_nomega = 0, map_nidx = 0, map_nslice = 0;
+  double2 *d_map_ws = nullptr, *d_map_out = nullptr;
+  double* d_map_omega = nullptr;
+  int *d_map_idx = nullptr, *d_map_slice = nullptr;
+  // what the last call with a dmap output left there, for dwh_bench_response_map_stages:
+  // slices, entries, frequencies per chunk, and where in d_rs_ws its last X lies
+  int64_t map_last_nslices = 0, map_last_npat = 0, map_last_chunk = 0, map_last_x = 0;
   // own eigensolver (dwhmc_eig.hip) workspace for eig_slots matrices: hemv
   // partials, v ping-pong, w, tridiagonal (d, e), tau, compact-WY T blocks and
   // the back-transform's two nb x n products; the n x n work lives in the

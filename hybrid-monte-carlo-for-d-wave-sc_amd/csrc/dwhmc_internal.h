@@ -436,6 +436,27 @@ void launch_nb_spec(const double2* X, int64_t sX, int N, const int* pairs, int p
                     const double* f, const double* g, double beta, double eta, double w_start, double w_step, int nw,
                     double* part, double* out, hipStream_t s);
 
+// Response maps (dwhmc_map.hip), one state at a time: D(z)[W] = U (w(z) ∘ X) U^H
+// with X = U^H W U, and ρ = U f U^H, at the entries of a sparse pattern.
+// Entries per workgroup of the sampled product (a longer column group is cut
+// into slices of this many)
+constexpr int kMapSlice = 32;
+// rows of the staged column the sampled product's LDS holds (128 KiB)
+constexpr int kMapMaxN2 = 8192;
+// K + c sK = w(z0 + c) ∘ X, c < cnt: z < nl the Matsubara index l = z
+// (launch_nb_pairs' r + i s), z >= nl the real frequency omega[z - nl] (device):
+// (f_n - f_m)/(ΔE_nm - ω - iη), 0 where |f_n - f_m| < 1e-12
+void launch_map_weight(const double2* X, int N, const double* E, const double* f, const double* g, double beta,
+                       int z0, int cnt, int nl, const double* omega, double eta, double2* K, int64_t sK,
+                       hipStream_t s);
+// S = diag(f) UH
+void launch_map_fscale(const double2* UH, int N, const double* f, double2* S, hipStream_t s);
+// out[dst[i] + y sOut] = Σ_n conj(UH[n, arow[i]]) S_y[n, b], S_y = S + y sS, y < nmat,
+// for every entry i of every slice (b, i0, cnt) (3 ints each: i0 <= i < i0 +
+// cnt <= i0 + kMapSlice); 2N <= kMapMaxN2
+void launch_map_sddmm(const double2* UH, const double2* S, int64_t sS, int N, const int* slices, int nslices,
+                      const int* arow, const int* dst, double2* out, int64_t sOut, int nmat, hipStream_t s);
+
 // Eigendecomposition leapfrog step (algo eig; U, JU, rho: nc chains of n2 x n2
 // column-major, E: nc x n2): JU = U diag(logistic(-β E)); after rho = JU U^H,
 // P at the bonds, Tr ρ_hh and E_f per chain

@@ -1,9 +1,9 @@
 // Measurement half of the C-ABI context (include/dwhmc.h), on the eigenpairs
 // of dwhmc_eigsolve.cpp: transport and spectra (dwhmc_transport.hip), the
-// spectral maps (dwhmc_spectral.hip) and the three vertex responses — current
+// spectral maps (dwhmc_spectral.hip) and the four vertex families — current
 // (dwhmc_response.hip), one-body operator (dwhmc_operator.hip), Nambu cross
-// response (dwhmc_nambu.hip) — which share one host vertex type, one upload
-// and one per-state driver; with their entry points.
+// response (dwhmc_nambu.hip), response maps (dwhmc_map.hip) — which share one
+// host vertex type, one upload and one per-state driver; with their entry points.
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
 
@@ -44,13 +44,19 @@ int64_t julia_range_len(double start, double step, double stop) {
 void response_release(dwh_ctx* ctx) {
   for (void* q : {(void*)ctx->d_rs_ws, (void*)ctx->d_rs_val, (void*)ctx->d_rs_part, (void*)ctx->d_rs_out,
                   (void*)ctx->d_rs_col, (void*)ctx->d_rs_idx, (void*)ctx->d_rs_nbr, (void*)ctx->d_op_part,
-                  (void*)ctx->d_nb_x, (void*)ctx->d_nb_part, (void*)ctx->d_nb_pairs})
+                  (void*)ctx->d_nb_x, (void*)ctx->d_nb_part, (void*)ctx->d_nb_pairs, (void*)ctx->d_map_ws,
+                  (void*)ctx->d_map_out, (void*)ctx->d_map_omega, (void*)ctx->d_map_idx, (void*)ctx->d_map_slice})
     drop_alloc(ctx, q);
   ctx->d_rs_ws = ctx->d_rs_val = ctx->d_nb_x = nullptr;
   ctx->d_rs_part = ctx->d_rs_out = ctx->d_op_part = ctx->d_nb_part = nullptr;
   ctx->d_rs_col = ctx->d_rs_idx = ctx->d_rs_nbr = ctx->d_nb_pairs = nullptr;
   ctx->rs_mats = ctx->rs_npart = ctx->rs_nout = ctx->rs_nval = ctx->rs_ncol = ctx->rs_nidx = ctx->rs_nnbr = 0;
   ctx->op_npart = ctx->nb_nx = ctx->nb_npart = ctx->nb_npairs = 0;
+  ctx->d_map_ws = ctx->d_map_out = nullptr;
+  ctx->d_map_omega = nullptr;
+  ctx->d_map_idx = ctx->d_map_slice = nullptr;
+  ctx->map_nws = ctx->map_nout = ctx->map_nomega = ctx->map_nidx = ctx->map_nslice = 0;
+  ctx->map_last_nslices = ctx->map_last_npat = ctx->map_last_chunk = ctx->map_last_x = 0;
 }
 
 }  // namespace
@@ -334,9 +340,10 @@ int spectral_run(dwh_ctx* ctx, const TrSrc& src, int m, double eta, double domeg
 // ---------------------------------------------------------------------------
 // The vertex responses (include/dwhmc.h): the current response Λ(q, iΩ)
 // (dwhmc_response.hip), the response of one-body operators (dwhmc_operator.hip)
-// and the cross response of Nambu vertices (dwhmc_nambu.hip).  Each turns its
-// arguments into a Vertex, and vertex_run takes it through the same steps:
-// W_k U, U^H (W_k U), the family's reductions.
+// the cross response of Nambu vertices (dwhmc_nambu.hip) and the response maps
+// on a pattern (dwhmc_map.hip).  Each turns its arguments into a Vertex, and
+// vertex_run takes it through the same steps: W_k U, U^H (W_k U), the family's
+// reductions.
 // ---------------------------------------------------------------------------
 
 // Cap of the matrix workspace of one group of vertices (W_k U and U^H W_k U,
@@ -498,13 +505,31 @@ int build_operator_nambu(dwh_ctx* ctx, int64_t N, int64_t nops, const int64_t* r
   return DWH_OK;
 }
 
+// The caller's 2N-row CSR of Nambu vertices (the cross response's and the
+// response maps'), checked; ctx may be NULL
+int check_nambu_csr(dwh_ctx* ctx, const std::string& pre, int64_t N, int64_t nops, const int64_t* rowptr,
+                    const int64_t* col, int64_t nnz, const dwh_c128* val) {
+  if (!rowptr || !col || !val) return fail(ctx, DWH_ERR_ARG, pre + ": NULL argument (rowptr, col or val)");
+  return check_csr(ctx, pre, "vertices", N, 2 * N, nops, rowptr, col, nnz);
+}
+
+// ... and as given, once checked
+void fill_nambu_vertices(int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
+                         const dwh_c128* val, Vertex* v) {
+  const int64_t n2 = 2 * N;
+  build_vertex((int)n2, nops, [&](int64_t k, auto&& emit) {
+    const dwh_c128* x = val + (size_t)k * nnz;
+    for (int64_t r = 0; r < n2; ++r)
+      for (int64_t e = rowptr[r]; e < rowptr[r + 1]; ++e) emit((int)r, (int)col[e], make_double2(x[e].re, x[e].im));
+  }, v);
+}
+
 // Nambu cross response: the caller's validated 2N-row CSR as given, and its
 // pair list checked; ctx may be NULL
 int build_nambu_vertices(dwh_ctx* ctx, int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col,
                          int64_t nnz, const dwh_c128* val, int64_t npairs, const int64_t* pairs, Vertex* v) {
-  if (!rowptr || !col || !val || !pairs)
-    return fail(ctx, DWH_ERR_ARG, "NULL argument (rowptr, col, val or pairs)");
-  if (int rc = check_csr(ctx, "nambu", "vertices", N, 2 * N, nops, rowptr, col, nnz)) return rc;
+  if (!pairs) return fail(ctx, DWH_ERR_ARG, "nambu: NULL argument (pairs)");
+  if (int rc = check_nambu_csr(ctx, "nambu", N, nops, rowptr, col, nnz, val)) return rc;
   if (npairs < 1 || npairs > kNbMaxPairs) return fail(ctx, DWH_ERR_ARG, "nambu: npairs must be in [1, 65535]");
   const int64_t n2 = 2 * N;
   for (int64_t k = 0; k < 2 * npairs; ++k)
@@ -512,11 +537,56 @@ int build_nambu_vertices(dwh_ctx* ctx, int64_t N, int64_t nops, const int64_t* r
       return fail(ctx, DWH_ERR_ARG, "nambu: pair index " + std::to_string(pairs[k]) + " outside [0, nops)");
   if ((double)nops * (double)n2 * (double)n2 * 16.0 > (double)kNbCapBytes)
     return fail(ctx, DWH_ERR_ARG, "nambu: " + std::to_string(nops) + " resident 2N x 2N matrices exceed 1 GiB");
-  build_vertex((int)n2, nops, [&](int64_t k, auto&& emit) {
-    const dwh_c128* x = val + (size_t)k * nnz;
-    for (int64_t r = 0; r < n2; ++r)
-      for (int64_t e = rowptr[r]; e < rowptr[r + 1]; ++e) emit((int)r, (int)col[e], make_double2(x[e].re, x[e].im));
-  }, v);
+  fill_nambu_vertices(N, nops, rowptr, col, nnz, val, v);
+  return DWH_OK;
+}
+
+// The pattern of a response-map call, npat Nambu index pairs (prow[e],
+// pcol[e]), grouped by column: order is the permutation of the entries sorted
+// by pcol, stable inside a column; the entries of column b are
+// order[colptr[b]] .. order[colptr[b + 1] - 1].  ctx may be NULL.
+constexpr int64_t kMapMaxPat = 1 << 24;
+struct MapPlan {
+  std::vector<int> order, colptr;
+};
+int map_plan(dwh_ctx* ctx, int64_t N, int64_t npat, const int64_t* prow, const int64_t* pcol, MapPlan* pl) {
+  const std::string pre = "response map";
+  if (N < 1 || N > (1 << 24)) return fail(ctx, DWH_ERR_ARG, pre + ": N must be in [1, 2^24]");
+  if (!prow || !pcol) return fail(ctx, DWH_ERR_ARG, pre + ": NULL argument (prow or pcol)");
+  if (npat < 1 || npat > kMapMaxPat) return fail(ctx, DWH_ERR_ARG, pre + ": npat must be in [1, 2^24]");
+  const int64_t n2 = 2 * N;
+  for (int64_t e = 0; e < npat; ++e)
+    if (prow[e] < 0 || prow[e] >= n2 || pcol[e] < 0 || pcol[e] >= n2)
+      return fail(ctx, DWH_ERR_ARG, pre + ": pattern entry " + std::to_string(e) + " (" + std::to_string(prow[e]) +
+                                        ", " + std::to_string(pcol[e]) + ") outside [0, 2N)");
+  pl->colptr.assign((size_t)n2 + 1, 0);
+  for (int64_t e = 0; e < npat; ++e) ++pl->colptr[(size_t)pcol[e] + 1];
+  for (int64_t b = 0; b < n2; ++b) pl->colptr[b + 1] += pl->colptr[b];
+  std::vector<int> next(pl->colptr.begin(), pl->colptr.end() - 1);
+  pl->order.resize((size_t)npat);
+  for (int64_t e = 0; e < npat; ++e) pl->order[(size_t)next[(size_t)pcol[e]]++] = (int)e;
+  return DWH_OK;
+}
+
+// counts and frequencies of a response-map call
+int map_args(dwh_ctx* ctx, int64_t N, int64_t nops, int64_t nl, double eta, int64_t nw, const double* omega,
+             const dwh_c128* rho, const dwh_c128* dmap) {
+  const std::string pre = "response map";
+  if (!rho && !dmap) return fail(ctx, DWH_ERR_ARG, pre + ": rho and dmap are both NULL");
+  if (nl < 0 || nw < 0) return fail(ctx, DWH_ERR_ARG, pre + ": n_matsubara and n_w must be >= 0");
+  if (nl > (1 << 16) || nw > (1 << 16) || nops * (nl + nw) > (1 << 20))
+    return fail(ctx, DWH_ERR_ARG, pre + ": more than 2^16 frequencies of a kind or 2^20 (vertex, frequency) points");
+  if (dmap && nl + nw == 0) return fail(ctx, DWH_ERR_ARG, pre + ": n_matsubara and n_w are both 0 with a dmap output");
+  if (2 * N > dwh::kMapMaxN2)
+    return fail(ctx, DWH_ERR_ARG, pre + ": 2N above " + std::to_string(dwh::kMapMaxN2) +
+                                      " (a staged column of the sampled product exceeds the LDS)");
+  if (nw > 0) {
+    if (!omega) return fail(ctx, DWH_ERR_ARG, pre + ": NULL omega with n_w > 0");
+    if (!std::isfinite(eta)) return fail(ctx, DWH_ERR_ARG, pre + ": eta must be finite");
+    if (!(eta > 0)) return fail(ctx, DWH_ERR_ARG, pre + ": eta must be > 0");
+    for (int64_t j = 0; j < nw; ++j)
+      if (!std::isfinite(omega[j])) return fail(ctx, DWH_ERR_ARG, pre + ": omega must be finite");
+  }
   return DWH_OK;
 }
 
@@ -582,13 +652,15 @@ int vertex_prepare(dwh_ctx* ctx, const Vertex& v, int64_t mats, int64_t npart, i
 // X holds the vertices k0 .. k0 + gk - 1), or into the resident d_nb_x,
 // reduced once after every group (reduce(b, X, 0, nk)).
 struct VertexFamily {
-  int timer;           // T_RESPONSE / T_OPERATOR / T_NAMBU
+  int timer;           // T_RESPONSE / T_OPERATOR / T_NAMBU / T_MAP
   int64_t nk;          // vertices of the call
   bool resident;
   int64_t npart, nout;   // elements of d_rs_part, results per state in d_rs_out
   std::function<int()> extras;                        // the family's own buffers and uploads
   std::function<void(const dwh::TrBufs&)> stats;      // f, g (and what else it takes from U, E) of a state
   std::function<void(const dwh::TrBufs&, const double2*, int64_t, int)> reduce;
+  std::function<void(const dwh::TrBufs&)> with_uh;   // (optional) what it takes from U^H alone, before any vertex
+  double extra_work = 0;                             // flops per state beyond the nk products of X
 };
 
 // The m states of src through the pipeline: one batched eigensolve, then per
@@ -615,10 +687,11 @@ int vertex_run(dwh_ctx* ctx, const TrSrc& src, int m, const Vertex& v, const Ver
   const double2 one = make_double2(1.0, 0.0), zero = make_double2(0.0, 0.0);
   out->resize((size_t)m * fam.nout);
   for (int k = 0; k < m; ++k) {
-    Scope sc(ctx, fam.timer, 8.0 * n2 * (double)n2 * n2 * fam.nk);
+    Scope sc(ctx, fam.timer, 8.0 * n2 * (double)n2 * n2 * fam.nk + fam.extra_work);
     const dwh::TrBufs b = tr_slot(ctx, k);
     fam.stats(b);
     dwh::launch_tr_conj_transpose(b.U, n2, n2, n2, 0, b.Jmn, n2, 0, 1, s);
+    if (fam.with_uh) fam.with_uh(b);
     for (int64_t k0 = 0; k0 < fam.nk; k0 += g) {
       const int gk = (int)std::min<int64_t>(g, fam.nk - k0);
       double2* X = fam.resident ? ctx->d_nb_x + k0 * sA : WU + (int64_t)g * sA;
@@ -628,8 +701,9 @@ int vertex_run(dwh_ctx* ctx, const TrSrc& src, int m, const Vertex& v, const Ver
     }
     if (fam.resident) fam.reduce(b, ctx->d_nb_x, 0, (int)fam.nk);
     HIPCHECK(ctx, hipGetLastError());
-    HIPCHECK(ctx, hipMemcpyAsync(out->data() + (size_t)k * fam.nout, ctx->d_rs_out, fam.nout * sizeof(double),
-                                 hipMemcpyDeviceToHost, s));
+    if (fam.nout > 0)
+      HIPCHECK(ctx, hipMemcpyAsync(out->data() + (size_t)k * fam.nout, ctx->d_rs_out, fam.nout * sizeof(double),
+                                   hipMemcpyDeviceToHost, s));
   }
   return eigen_info_check(ctx, m);   // (synchronises)
 }
@@ -736,6 +810,102 @@ int nambu_run(dwh_ctx* ctx, const TrSrc& src, int m, const Vertex& v, int64_t no
     if (nw > 0) std::copy(o + np * nl, o + np * (nl + nw), chi2 + (size_t)k * np * nw);
   }
   return DWH_OK;
+}
+
+// frequencies per chunk of a response-map call: the chunk's K_z and S_z = K_z U^H
+// within kRsCapBytes and its sampled entries within 1 GiB; one frequency is
+// always allowed (DWHMC_MAP_CHUNK: a smaller chunk, for tests of the chunk loop)
+int map_chunk(const dwh_ctx* ctx, int64_t nz, int64_t npat) {
+  const double n2 = 2.0 * ctx->d.N;
+  int c = (int)std::min<double>(kRsMaxGroup, kRsCapBytes / (2.0 * 16.0 * n2 * n2));
+  c = (int)std::min<int64_t>(c, (1ll << 26) / npat);
+  if (const char* e = std::getenv("DWHMC_MAP_CHUNK")) c = std::min(c, std::atoi(e));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(c, nz));
+}
+
+// rho[e] and dmap[e + npat (z + nz k)] of the m states of src (host, per state
+// npat and npat nz nops complex; either nullable).  Per state ρ from
+// S = diag(f) U^H, then per vertex of a group and per chunk of frequencies:
+// K_z = w(z) ∘ X (launch_map_weight), S_z = K_z U^H (the batched product, U^H
+// at stride 0) and the sampled product on the column-grouped pattern, copied
+// out chunk by chunk.  Without dmap no vertex is applied (nk = 0).
+int map_run(dwh_ctx* ctx, const TrSrc& src, int m, const Vertex& v, int64_t nops, const MapPlan& pl,
+            const int64_t* prow, int64_t nl, double eta, const std::vector<double>& omega, dwh_c128* rho,
+            dwh_c128* dmap) {
+  const int N = ctx->d.N, n2 = 2 * N;
+  const int64_t sA = (int64_t)n2 * n2, npat = (int64_t)pl.order.size(), nw = (int64_t)omega.size(), nz = nl + nw;
+  const int chunk = dmap ? map_chunk(ctx, nz, npat) : 0;
+  hipStream_t s = ctx->stream;
+  // the pattern as the kernel reads it: row a and original index of every
+  // grouped entry, and the column groups cut into workgroup slices (b, first, count)
+  std::vector<int> idx(2 * (size_t)npat), slices;
+  for (int64_t i = 0; i < npat; ++i) {
+    idx[(size_t)i] = (int)prow[pl.order[(size_t)i]];
+    idx[(size_t)(npat + i)] = pl.order[(size_t)i];
+  }
+  for (int b = 0; b < n2; ++b)
+    for (int i = pl.colptr[b]; i < pl.colptr[b + 1]; i += dwh::kMapSlice)
+      slices.insert(slices.end(), {b, i, std::min(dwh::kMapSlice, pl.colptr[b + 1] - i)});
+  const int nslices = (int)(slices.size() / 3);
+  int state = -1, lrc = DWH_OK;
+  auto copy_out = [&](dwh_c128* dst, int64_t count) {
+    if (lrc == DWH_OK && hipMemcpyAsync(dst, ctx->d_map_out, (size_t)count * sizeof(double2), hipMemcpyDeviceToHost,
+                                        s) != hipSuccess)
+      lrc = fail(ctx, DWH_ERR_HIP, "response map: copying the sampled entries out failed");
+  };
+  VertexFamily fam{T_MAP, dmap ? nops : 0, false, 0, 0};
+  fam.extra_work = dmap ? 8.0 * n2 * (double)n2 * n2 * (double)(nops * nz) : 0.0;
+  fam.extras = [&]() -> int {
+    int rc;
+    if ((rc = rs_grow(ctx, &ctx->d_map_ws, &ctx->map_nws, std::max<int64_t>(2 * chunk, 1) * sA)) ||
+        (rc = rs_grow(ctx, &ctx->d_map_out, &ctx->map_nout, std::max<int64_t>(chunk, 1) * npat)) ||
+        (rc = rs_grow(ctx, &ctx->d_map_omega, &ctx->map_nomega, nw)) ||
+        (rc = rs_grow(ctx, &ctx->d_map_idx, &ctx->map_nidx, 2 * npat)) ||
+        (rc = rs_grow(ctx, &ctx->d_map_slice, &ctx->map_nslice, (int64_t)slices.size())))
+      return rc;
+    if (nw > 0)
+      HIPCHECK(ctx, hipMemcpyAsync(ctx->d_map_omega, omega.data(), nw * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHECK(ctx, hipMemcpyAsync(ctx->d_map_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHECK(ctx, hipMemcpyAsync(ctx->d_map_slice, slices.data(), slices.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    return DWH_OK;
+  };
+  fam.stats = [&](const dwh::TrBufs& b) {
+    ++state;
+    dwh::launch_op_fermi(b.E, N, ctx->beta, b.f, b.g, s);
+  };
+  auto sample = [&](const dwh::TrBufs& b, const double2* S, int nmat) {
+    dwh::launch_map_sddmm(b.Jmn, S, sA, N, ctx->d_map_slice, nslices, ctx->d_map_idx, ctx->d_map_idx + npat,
+                          ctx->d_map_out, npat, nmat, s);
+  };
+  fam.with_uh = [&](const dwh::TrBufs& b) {
+    if (!rho) return;
+    dwh::launch_map_fscale(b.Jmn, N, b.f, ctx->d_map_ws, s);
+    sample(b, ctx->d_map_ws, 1);
+    copy_out(rho + (size_t)state * npat, npat);
+  };
+  fam.reduce = [&](const dwh::TrBufs& b, const double2* X, int64_t k0, int gk) {
+    const double2 one = make_double2(1.0, 0.0), zero = make_double2(0.0, 0.0);
+    double2 *K = ctx->d_map_ws, *S = ctx->d_map_ws + (int64_t)chunk * sA;
+    for (int j = 0; j < gk; ++j)
+      for (int64_t z0 = 0; z0 < nz; z0 += chunk) {
+        const int c = (int)std::min<int64_t>(chunk, nz - z0);
+        dwh::launch_map_weight(X + (int64_t)j * sA, N, b.E, b.f, b.g, ctx->beta, (int)z0, c, (int)nl,
+                               ctx->d_map_omega, eta, K, sA, s);
+        dwh::gemm_z('N', 'N', n2, n2, n2, one, K, n2, sA, b.Jmn, n2, 0, zero, S, n2, sA, c, s);
+        sample(b, S, c);
+        copy_out(dmap + (size_t)npat * (z0 + nz * (k0 + j + nops * (int64_t)state)), c * npat);
+      }
+  };
+  std::vector<double> out;
+  ctx->map_last_chunk = 0;
+  if (int rc = vertex_run(ctx, src, m, v, fam, &out)) return rc;
+  if (dmap && lrc == DWH_OK) {
+    ctx->map_last_nslices = nslices;
+    ctx->map_last_npat = npat;
+    ctx->map_last_chunk = chunk;
+    ctx->map_last_x = (int64_t)rs_group(ctx, nops) * sA;
+  }
+  return lrc;
 }
 
 
@@ -940,6 +1110,83 @@ int dwh_debug_nambu_dense(int64_t N, int64_t nops, const int64_t* rowptr, const 
   return DWH_OK;
 }
 
+int dwh_measure_response_map(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta, int64_t nops,
+                             const int64_t* rowptr, const int64_t* col, int64_t nnz, const dwh_c128* val,
+                             int64_t npat, const int64_t* prow, const int64_t* pcol, int64_t n_matsubara, double eta,
+                             int64_t n_w, const double* omega, dwh_c128* rho, dwh_c128* dmap) {
+  if (!ctx) return fail(nullptr, DWH_ERR_ARG, "NULL context");
+  int rc;
+  if ((rc = check_state_args(ctx, chain, nstates, Delta))) return rc;
+  const int64_t N = ctx->d.N;
+  if ((rc = check_nambu_csr(ctx, "response map", N, nops, rowptr, col, nnz, val))) return rc;
+  if ((rc = map_args(ctx, N, nops, n_matsubara, eta, n_w, omega, rho, dmap))) return rc;
+  MapPlan pl;
+  if ((rc = map_plan(ctx, N, npat, prow, pcol, &pl))) return rc;
+  Vertex v;
+  fill_nambu_vertices(N, nops, rowptr, col, nnz, val, &v);
+  const std::vector<double> w(omega, omega + (n_w > 0 ? n_w : 0));
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  SETTLE(ctx);
+  const int64_t nz = n_matsubara + n_w;
+  return for_each_state_group(ctx, chain, nstates, Delta, [&](const TrSrc& src, int m, int64_t s0) {
+    return map_run(ctx, src, m, v, nops, pl, prow, n_matsubara, eta, w, rho ? rho + (size_t)s0 * npat : nullptr,
+                   dmap ? dmap + (size_t)s0 * nops * nz * npat : nullptr);
+  });
+}
+
+int dwh_debug_response_map_plan(int64_t N, int64_t npat, const int64_t* prow, const int64_t* pcol, int64_t* order,
+                                int64_t* colptr) {
+  if (!order || !colptr) return fail(nullptr, DWH_ERR_ARG, "response map: NULL argument (order or colptr)");
+  MapPlan pl;
+  if (int rc = map_plan(nullptr, N, npat, prow, pcol, &pl)) return rc;
+  std::copy(pl.order.begin(), pl.order.end(), order);
+  std::copy(pl.colptr.begin(), pl.colptr.end(), colptr);
+  return DWH_OK;
+}
+
+int dwh_bench_response_map_stages(dwh_ctx* ctx, int64_t reps, int64_t nfreq, double* weight_ms, double* sample_ms) {
+  if (!ctx || !weight_ms || !sample_ms) return fail(ctx, DWH_ERR_ARG, "NULL argument");
+  if (reps < 1 || reps > 1000) return fail(ctx, DWH_ERR_ARG, "reps must be in [1, 1000]");
+  if (ctx->map_last_chunk < 1 || !ctx->d_map_ws || !ctx->d_rs_ws)
+    return fail(ctx, DWH_ERR_STATE, "no response map with a dmap output has run on this context yet");
+  if (nfreq < 1 || nfreq > ctx->map_last_chunk)
+    return fail(ctx, DWH_ERR_ARG, "nfreq must be in [1, " + std::to_string(ctx->map_last_chunk) +
+                                      "], the last call's frequencies per chunk");
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  SETTLE(ctx);
+  const int N = ctx->d.N, n2 = 2 * N;
+  const int64_t sA = (int64_t)n2 * n2, npat = ctx->map_last_npat;
+  const dwh::TrBufs& b = ctx->tr;
+  hipStream_t s = ctx->stream;
+  double2 *K = ctx->d_map_ws, *S = ctx->d_map_ws + ctx->map_last_chunk * sA;
+  const int c = (int)nfreq;
+  // the last call's X, K_z, S_z, U^H and pattern, as it left them (Matsubara weights l < nfreq)
+  auto weight = [&]() {
+    dwh::launch_map_weight(ctx->d_rs_ws + ctx->map_last_x, N, b.E, b.f, b.g, ctx->beta, 0, c, c, nullptr, 1.0, K, sA, s);
+  };
+  auto sample = [&]() {
+    dwh::launch_map_sddmm(b.Jmn, S, sA, N, ctx->d_map_slice, (int)ctx->map_last_nslices, ctx->d_map_idx,
+                          ctx->d_map_idx + npat, ctx->d_map_out, npat, c, s);
+  };
+  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+  for (auto& ev : e) HIPCHECK(ctx, hipEventCreate(&ev));
+  weight();   // warm
+  sample();
+  HIPCHECK(ctx, hipEventRecord(e[0], s));
+  for (int64_t r = 0; r < reps; ++r) weight();
+  HIPCHECK(ctx, hipEventRecord(e[1], s));
+  for (int64_t r = 0; r < reps; ++r) sample();
+  HIPCHECK(ctx, hipEventRecord(e[2], s));
+  HIPCHECK(ctx, hipStreamSynchronize(s));
+  HIPCHECK(ctx, hipGetLastError());
+  float tw = 0.f, ts = 0.f;
+  HIPCHECK(ctx, hipEventElapsedTime(&tw, e[0], e[1]));
+  HIPCHECK(ctx, hipEventElapsedTime(&ts, e[1], e[2]));
+  for (auto& ev : e) (void)hipEventDestroy(ev);
+  *weight_ms = (double)tw / (double)reps;
+  *sample_ms = (double)ts / (double)reps;
+  return DWH_OK;
+}
 
 int dwh_bench_response_product(dwh_ctx* ctx, int64_t reps, double* ms) {
   if (!ctx || !ms) return fail(ctx, DWH_ERR_ARG, "NULL argument");

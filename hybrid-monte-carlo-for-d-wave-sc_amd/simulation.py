@@ -198,6 +198,51 @@ def _nambu_opts(nambu_response: dict, p) -> dict:
                       eta=float(nambu_response.get("eta", p.eta)))
 
 
+class _MapOpts(dict):
+    """a `response_map` option after _map_opts parsed it"""
+
+
+def _map_opts(response_map: dict, p) -> dict:
+    """vertices / pattern / n_matsubara / omega / eta of a run's `response_map`
+    option: the source vertices built once (vertices.build_nambu), the pattern
+    from dict(ranges=, blocks=) (vertices.bond_pattern; None: all of it) or an
+    (npat, 2) integer array, omega a list of real frequencies or None, eta
+    defaulting to the run's.  Options parsed before are returned as they are."""
+    if isinstance(response_map, _MapOpts):
+        return response_map
+    extra = set(response_map) - {"vertices", "pattern", "n_matsubara", "omega", "eta"}
+    if extra:
+        raise ValueError(f"response_map: unknown keys {sorted(extra)}")
+    names = [(str(kind), (int(m[0]), int(m[1])))
+             for kind, m in response_map.get("vertices", [("current_x", (0, 0))])]
+    if not names:
+        raise ValueError("response_map: vertices is empty")
+    verts = [VX.build_nambu(kind, p, mx, my) for kind, (mx, my) in names]
+    pattern = response_map.get("pattern")
+    if pattern is None or isinstance(pattern, dict):
+        bad = set(pattern or {}) - {"ranges", "blocks"}
+        if bad:
+            raise ValueError(f"response_map: unknown pattern keys {sorted(bad)}")
+        pattern = VX.bond_pattern(p, **(pattern or {}))
+    pattern = np.asarray(pattern)
+    if pattern.ndim != 2 or pattern.shape[1] != 2 or len(pattern) < 1 or not np.issubdtype(pattern.dtype, np.integer) \
+            or pattern.min() < 0 or pattern.max() >= 2 * p.N:
+        raise ValueError("response_map: pattern must be a non-empty (npat, 2) integer array of indices in [0, 2N)")
+    omega = response_map.get("omega")
+    omega = None if omega is None else [float(w) for w in omega]
+    nl = int(response_map.get("n_matsubara", 1))
+    if nl < 0 or (nl == 0 and not omega):
+        raise ValueError("response_map: n_matsubara >= 0, and a list of frequencies when it is 0")
+    return _MapOpts(names=names, vertices=verts, pattern=np.ascontiguousarray(pattern, dtype=np.int64),
+                    n_matsubara=nl, omega=omega or None, eta=float(response_map.get("eta", p.eta)))
+
+
+def write_map_header(spec_dir: str, opts: dict) -> None:
+    """response_map_pattern.npy: the (npat, 2) pattern of the response_map option."""
+    os.makedirs(spec_dir, exist_ok=True)
+    np.save(os.path.join(spec_dir, "response_map_pattern.npy"), opts["pattern"])
+
+
 def nambu_csv_header(opts: dict) -> str:
     """sweep, then re and im of chi pair by pair, l fastest, named by the pair's
     two vertices (kind and momentum) and l."""
@@ -236,8 +281,10 @@ class SpectraBins:
     bin_size measurements, then writes their mean as group sweep_<i>.  With
     spectral maps (add's `maps`: the ldos / akw of that measurement, each
     (count, Ly, Lx)) the group also holds their bin means, summed the same way;
-    so it does for chi2 ((nops, n_w)) of the operator_response option and the
-    complex nambu_chi2 ((npairs, n_w)) of the nambu_response option."""
+    so it does for chi2 ((nops, n_w)) of the operator_response option, the
+    complex nambu_chi2 ((npairs, n_w)) of the nambu_response option and the
+    complex response_map ((nops, nz, npat)) and rho_map ((npat,)) of the
+    response_map option."""
 
     def __init__(self):
         self.count = 0
@@ -397,17 +444,22 @@ class TransportQueue:
     nambu_response (vertices / pairs / n_matsubara / omega / eta, or None):
     every measurement also appends its row (sweep, re and im of chi) to
     nambu_response.csv and puts the complex chi2 into the bins as nambu_chi2
-    (measure_nambu_response, batched the same way)."""
+    (measure_nambu_response, batched the same way).  response_map (vertices /
+    pattern / n_matsubara / omega / eta, or None): every measurement also puts
+    the complex dmap and ρ on the pattern into the bins as response_map and
+    rho_map (measure_response_map, batched the same way)."""
 
     def __init__(self, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int, chain: int = 0,
                  spectral_maps: dict | None = None, current_response: dict | None = None,
-                 operator_response: dict | None = None, nambu_response: dict | None = None):
+                 operator_response: dict | None = None, nambu_response: dict | None = None,
+                 response_map: dict | None = None):
         self.ctx, self.p, self.out, self.res = ctx, p, out, res
         self.bin_size, self.batch, self.chain = bin_size, max(1, int(batch)), chain
         self.window = None if spectral_maps is None else _maps_window(spectral_maps)
         self.response = None if current_response is None else _response_opts(current_response)
         self.operator = None if operator_response is None else _operator_opts(operator_response, p)
         self.nambu = None if nambu_response is None else _nambu_opts(nambu_response, p)
+        self.rmap = None if response_map is None else _map_opts(response_map, p)
         self.pending = []            # (sweep, Δ snapshot)
 
     def add(self, sweep: int, Delta):
@@ -443,6 +495,10 @@ class TransportQueue:
         if self.nambu is not None:
             deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
             nam = measure_nambu_option(self.ctx, self.nambu, self.chain, deltas)
+        rmap = None
+        if self.rmap is not None:
+            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
+            rmap = measure_map_option(self.ctx, self.rmap, self.chain, deltas)
         for k, ((i, _), r) in enumerate(zip(self.pending, specs)):
             spec = H.SpectrumResult(**r)
             extra = None if maps is None else {"ldos": maps["ldos"][k], "akw": maps["akw"][k]}
@@ -450,6 +506,8 @@ class TransportQueue:
                 extra = dict(extra or {}, chi2=oper["chi2"][k])
             if nam is not None and self.nambu["omega"] is not None:
                 extra = dict(extra or {}, nambu_chi2=nam["chi2"][k])
+            if rmap is not None:
+                extra = dict(extra or {}, response_map=rmap["dmap"][k], rho_map=rmap["rho"][k])
             self.out.transport(i, spec, self.bin_size, extra)
             self.res.transport.append((i, spec))
             if resp is not None:
@@ -483,6 +541,17 @@ def measure_nambu_option(ctx, opts: dict, chain: int, deltas) -> dict:
     return r
 
 
+def measure_map_option(ctx, opts: dict, chain: int, deltas) -> dict:
+    """measure_response_map for the response_map option: complex dmap
+    (nstates, nops, nz, npat) and rho (nstates, npat), one state at the device
+    Δ when deltas is None."""
+    r = ctx.measure_response_map(opts["vertices"], opts["pattern"], n_matsubara=opts["n_matsubara"],
+                                 omega=opts["omega"], eta=opts["eta"], chain=chain, deltas=deltas)
+    if deltas is None:
+        return dict(dmap=r["dmap"][None], rho=r["rho"][None])
+    return r
+
+
 def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_measure: int = 500,
                    Nt_therm_init: int = 10, Nt_measure: int = 5, measure_transport_freq: int = 1,
                    bin_size: int = 5, verbose: bool = True, rng: np.random.Generator | None = None,
@@ -490,7 +559,7 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
                    cache: H.ComputeCache | None = None, transport_batch: int = 1,
                    spectral_maps: dict | None = None, current_response: dict | None = None,
                    operator_response: dict | None = None,
-                   nambu_response: dict | None = None) -> SimulationResult:
+                   nambu_response: dict | None = None, response_map: dict | None = None) -> SimulationResult:
     """src/Simulation.jl:34-236.  Files in out_dir: simulation.log (appended),
     observables.csv, transport.csv (one row per transport measurement, every
     measure_transport_freq sweeps; <= 0 disables), and spectra_bins/ — the
@@ -529,12 +598,22 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
     vertices and l, and with an omega grid each sweep_<i>.npz gains the complex
     bin mean nambu_chi2 ((npairs, count)) with the grid in
     spectra_bins/nambu_chi2_omega.npy.  None (the default): no such files,
-    everything else as without the option."""
+    everything else as without the option.
+    response_map = dict(vertices=[(kind, (mx, my)), ...], pattern=dict(ranges=,
+    blocks=) or an (npat, 2) array, n_matsubara=, omega=[ω, ...], eta=) (each
+    optional; kind a key of vertices.NAMBU_KINDS, default the q = 0 x current
+    on the whole vertices.bond_pattern; FermionContext.measure_response_map):
+    every transport measurement also takes the linear-response density matrix
+    of each source vertex and ρ on the pattern; each sweep_<i>.npz gains their
+    complex bin means response_map ((nops, nz, npat)) and rho_map ((npat,)),
+    and spectra_bins/response_map_pattern.npy holds the pattern.  None (the
+    default): no such files, everything else as without the option."""
     rng = rng if rng is not None else np.random.default_rng()
     if current_response is not None:
         _response_opts(current_response)
     oper_opts = None if operator_response is None else _operator_opts(operator_response, p)
     nambu_opts = None if nambu_response is None else _nambu_opts(nambu_response, p)
+    map_opts = None if response_map is None else _map_opts(response_map, p)
     out = ChainOutput(out_dir, verbose)
     try:
         out.header(p, n_therm, n_measure, measure_transport_freq, bin_size)
@@ -553,6 +632,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
                 write_chi2_header(out.spec_dir, oper_opts)
             if nambu_opts is not None:
                 write_nambu_header(out.spec_dir, nambu_opts)
+            if map_opts is not None:
+                write_map_header(out.spec_dir, map_opts)
         Nt_fin, acc_th = thermalize(cache, p, state, out, n_therm, Nt_therm_init, rng)
 
         dt_meas = H.calc_optimal_dt(p.beta, p.J, p.mass, Nt_measure)
@@ -563,7 +644,7 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         res = SimulationResult(Nt_fin, acc_th, 0.0)
         tq = TransportQueue(cache.require(), p, out, res, bin_size, transport_batch, spectral_maps=spectral_maps,
                             current_response=current_response, operator_response=operator_response,
-                            nambu_response=nambu_opts)
+                            nambu_response=nambu_opts, response_map=map_opts)
         for i in range(1, n_measure + 1):
             acc, dH = H.hmc_sweep(cache, p, state, Nt=Nt_measure, dt=dt_meas, rng=rng)
             acc_total += int(acc)
@@ -588,7 +669,7 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                           delta_cap: float = 0.0, transport_batch: int = 1,
                           spectral_maps: dict | None = None, current_response: dict | None = None,
                           operator_response: dict | None = None,
-                          nambu_response: dict | None = None) -> list:
+                          nambu_response: dict | None = None, response_map: dict | None = None) -> list:
     """len(out_dirs) independent run_simulation's (src/Simulation.jl:34-236),
     chain k writing out_dirs[k] and drawing from rngs[k] in the reference's
     order (initialize_state, then per sweep randn(ComplexF64) and rand() only
@@ -605,12 +686,13 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
     largest spectral bound over the chains, and a guard trip re-selects it
     for every chain, so dH differs at ~1e-12 and a Metropolis decision can
     differ).  spectral_maps, current_response, operator_response,
-    nambu_response: as run_simulation's, for every chain."""
+    nambu_response, response_map: as run_simulation's, for every chain."""
     K = len(out_dirs)
     window = None if spectral_maps is None else _maps_window(spectral_maps)
     response = None if current_response is None else _response_opts(current_response)
     oper_opts = None if operator_response is None else _operator_opts(operator_response, p)
     nambu_opts = None if nambu_response is None else _nambu_opts(nambu_response, p)
+    map_opts = None if response_map is None else _map_opts(response_map, p)
     if len(rngs) != K or K < 1:
         raise ValueError("one rng per output directory")
     outs = [ChainOutput(d, verbose) for d in out_dirs]
@@ -631,6 +713,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                     write_chi2_header(outs[k].spec_dir, oper_opts)
                 if nambu_opts is not None:
                     write_nambu_header(outs[k].spec_dir, nambu_opts)
+                if map_opts is not None:
+                    write_map_header(outs[k].spec_dir, map_opts)
             Nt_fin, acc_th = thermalize(cache, p, st, outs[k], n_therm, Nt_therm_init, rngs[k])
             cache.ctx.close()
             states.append(st)
@@ -650,7 +734,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
             acc_total = np.zeros(K, dtype=np.int64)
             tqs = [TransportQueue(ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k,
                                   spectral_maps=spectral_maps, current_response=current_response,
-                                  operator_response=operator_response, nambu_response=nambu_opts)
+                                  operator_response=operator_response, nambu_response=nambu_opts,
+                                  response_map=map_opts)
                    for k in range(K)] if transport_batch > 1 else None
             for i in range(1, n_measure + 1):
                 noise = np.stack([H.standard_complex_normal(r, (p.N, 2)) for r in rngs])
@@ -683,6 +768,9 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                         nam = None if nambu_opts is None else measure_nambu_option(ctx, nambu_opts, k, None)
                         if nam is not None and nambu_opts["omega"] is not None:
                             maps = dict(maps or {}, nambu_chi2=nam["chi2"][0])
+                        if map_opts is not None:
+                            rm = measure_map_option(ctx, map_opts, k, None)
+                            maps = dict(maps or {}, response_map=rm["dmap"][0], rho_map=rm["rho"][0])
                         outs[k].transport(i, spec, bin_size, maps)
                         results[k].transport.append((i, spec))
                         if response is not None:

@@ -30,6 +30,15 @@ COO triplets of any complex 2N x 2N matrix W, the operator Ψ† W Ψ in the bas
                          C + C†, "phase": i (C - C†)
     hamiltonian          H_BdG(Δ) itself, entry for entry what the device assembles
     commutator_with_h    i (H W - W H)
+
+For FermionContext.measure_response_map, which samples the linear-response
+density matrix D(z)[W] and ρ on a pattern of Nambu index pairs (a, b):
+
+    bond_pattern         (npat, 2): every site with its 4 + 4 neighbours, per block
+    contract             Σ_e conj(B_e) D_e = N·chi of the pair (W, B)
+    diamagnetic_map,     the local dia_i, Λ_i and stiffness dia_i - Λ_i from ρ and
+    paramagnetic_map,    D(0)[J_α(q = 0)]; their site means are the current
+    stiffness_map        response's dia, Λ(q = 0, l = 0) and the stiffness
 """
 from __future__ import annotations
 
@@ -96,14 +105,17 @@ def spin(p, mx: int = 0, my: int = 0) -> Vertex:
     return density(p, mx, my)._replace(spin_sign=-1)
 
 
-def current(p, mx: int = 0, my: int = 0, direction="x") -> Vertex:
+def _current_bonds(p, direction):
+    """(name, t_b) of the bond list of direction α of dwh_measure_current_response."""
     if direction not in ("x", "y", 0, 1):
         raise ValueError("direction must be 'x' or 'y'")
     if direction in ("x", 0):
-        bonds = [("+x", p.t), ("+x+y", p.tp), ("+x-y", p.tp)]
-    else:
-        bonds = [("+y", p.t), ("+x+y", p.tp), ("-x+y", p.tp)]
-    return _bond_vertex(p, mx, my, bonds, -1.0, 1j)
+        return [("+x", p.t), ("+x+y", p.tp), ("+x-y", p.tp)]
+    return [("+y", p.t), ("+x+y", p.tp), ("-x+y", p.tp)]
+
+
+def current(p, mx: int = 0, my: int = 0, direction="x") -> Vertex:
+    return _bond_vertex(p, mx, my, _current_bonds(p, direction), -1.0, 1j)
 
 
 def raman_b1g(p, mx: int = 0, my: int = 0) -> Vertex:
@@ -342,3 +354,120 @@ def build_nambu(kind: str, p, mx: int = 0, my: int = 0) -> NambuVertex:
     if kind not in NAMBU_KINDS:
         raise ValueError(f"unknown Nambu vertex kind {kind!r}; one of {sorted(NAMBU_KINDS)}")
     return NAMBU_KINDS[kind](p, int(mx), int(my))
+
+
+# --------------------------------------------------------------------------
+# patterns and contractions (FermionContext.measure_response_map)
+# --------------------------------------------------------------------------
+PATTERN_RANGES = ("site", "nn", "nnn")
+PATTERN_BLOCKS = {"pp": (0, 0), "hh": (1, 1), "ph": (0, 1), "hp": (1, 0)}
+
+
+def bond_pattern(p, ranges=PATTERN_RANGES, blocks=tuple(PATTERN_BLOCKS)) -> np.ndarray:
+    """(npat, 2) Nambu index pairs (a, b): per block, every site's (i, i)
+    ("site"), (i, j) over its 4 nearest ("nn") and 4 next-nearest ("nnn")
+    neighbours j; block "pp" is (i, j), "hh" (i + N, j + N), "ph" (i, j + N),
+    "hp" (i + N, j).  9N entries per block with all three ranges; on rings
+    shorter than 3 a neighbour repeats and so does its entry."""
+    ranges, blocks = tuple(ranges), tuple(blocks)
+    for r in ranges:
+        if r not in PATTERN_RANGES:
+            raise ValueError(f"unknown range {r!r}; one of {PATTERN_RANGES}")
+    for b in blocks:
+        if b not in PATTERN_BLOCKS:
+            raise ValueError(f"unknown block {b!r}; one of {tuple(PATTERN_BLOCKS)}")
+    if not ranges or not blocks:
+        raise ValueError("bond_pattern: ranges and blocks must not be empty")
+    N = p.N
+    i = np.arange(N, dtype=np.int64)
+    nn, nnn = np.asarray(p.nn_table, dtype=np.int64) - 1, np.asarray(p.nnn_table, dtype=np.int64) - 1
+    rows, cols = [], []
+    for r in ranges:
+        if r == "site":
+            rows.append(i)
+            cols.append(i)
+        else:
+            tab = nn if r == "nn" else nnn
+            for d in range(4):
+                rows.append(i)
+                cols.append(tab[:, d])
+    a, b = np.concatenate(rows), np.concatenate(cols)
+    out = [np.stack([a + N * PATTERN_BLOCKS[k][0], b + N * PATTERN_BLOCKS[k][1]], axis=1) for k in blocks]
+    return np.ascontiguousarray(np.concatenate(out), dtype=np.int64)
+
+
+def _pattern_index(pattern, n2: int, rows, cols, what: str) -> np.ndarray:
+    """index into the pattern of every (rows[k], cols[k]) (a duplicated
+    pattern entry: its first copy); ValueError if one is missing"""
+    pat = np.asarray(pattern, dtype=np.int64).reshape(-1, 2)
+    keys = pat[:, 0] * n2 + pat[:, 1]
+    order = np.argsort(keys, kind="stable")
+    want = np.asarray(rows, dtype=np.int64) * n2 + np.asarray(cols, dtype=np.int64)
+    pos = np.searchsorted(keys[order], want)
+    ok = pos < len(keys)
+    ok[ok] = keys[order][pos[ok]] == want[ok]
+    if not np.all(ok):
+        k = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f"{what}: entry ({int(want[k] // n2)}, {int(want[k] % n2)}) is not in the pattern")
+    return order[pos]
+
+
+def contract(pattern, D, B, N=None):
+    """Σ_e conj(B_e) D_e over the entries of the vertex B (a NambuVertex, or a
+    Vertex lifted by `nambu`; duplicates summed first), D (..., npat) on
+    `pattern`: N·chi of the pair (W, B) for D = dmap of W.  N (sites, or
+    anything with .N) is needed for a Vertex and else taken from the largest
+    index.  ValueError if an entry of B is missing from the pattern."""
+    pat = np.asarray(pattern, dtype=np.int64).reshape(-1, 2)
+    if isinstance(B, Vertex):
+        if N is None:
+            raise ValueError("contract: N is needed to lift a Vertex")
+        B = nambu(B, N)
+    r, c, v = (np.asarray(a).ravel() for a in (B.row, B.col, B.val))
+    n2 = 2 * int(getattr(N, "N", N)) if N is not None else int(max(pat.max(), r.max(), c.max())) + 1
+    keys, inv = np.unique(r.astype(np.int64) * n2 + c.astype(np.int64), return_inverse=True)
+    val = np.zeros(len(keys), dtype=np.complex128)
+    np.add.at(val, inv, v)
+    idx = _pattern_index(pat, n2, keys // n2, keys % n2, "contract")
+    return np.asarray(D)[..., idx] @ np.conj(val)
+
+
+def _map_bonds(p, direction):
+    """(j_b, t_b) per bond of direction α's current: site i owns the bonds that start at i."""
+    lists = _bond_lists(p)
+    return [(np.asarray(lists[name][0], dtype=np.int64), float(t)) for name, t in _current_bonds(p, direction)]
+
+
+def diamagnetic_map(p, pattern, rho, direction="x") -> np.ndarray:
+    """dia_i = Σ_b t_b 2 Re(ρ[j_b, i] - ρ[N + i, N + j_b]) per site i from ρ
+    (npat,) on `pattern` (measure_response_map's rho); its mean over the sites
+    is measure_current_response's dia."""
+    N, rho = p.N, np.asarray(rho)
+    i = np.arange(N, dtype=np.int64)
+    out = np.zeros(N)
+    for j, t in _map_bonds(p, direction):
+        pp = rho[_pattern_index(pattern, 2 * N, j, i, "diamagnetic_map")]
+        hh = rho[_pattern_index(pattern, 2 * N, N + i, N + j, "diamagnetic_map")]
+        out += t * 2 * np.real(pp - hh)
+    return out
+
+
+def paramagnetic_map(p, pattern, D, direction="x") -> np.ndarray:
+    """Λ_i = Σ_b Σ_{o in {0, N}} Re[conj(i t_b)(D[o + i, o + j_b] - D[o + j_b, o + i])]
+    per site i from D (npat,) = dmap at l = 0 of the source nambu(current(p, 0,
+    0, α)); its mean over the sites is Λ_αα(q = 0, l = 0)."""
+    N, D = p.N, np.asarray(D)
+    i = np.arange(N, dtype=np.int64)
+    out = np.zeros(N)
+    for j, t in _map_bonds(p, direction):
+        for o in (0, N):
+            fw = D[_pattern_index(pattern, 2 * N, o + i, o + j, "paramagnetic_map")]
+            bw = D[_pattern_index(pattern, 2 * N, o + j, o + i, "paramagnetic_map")]
+            out += np.real(np.conj(1j * t) * (fw - bw))
+    return out
+
+
+def stiffness_map(p, pattern, rho, D, direction="x") -> np.ndarray:
+    """dia_i - Λ_i: the local superfluid stiffness, whose mean over the sites
+    is the stiffness of the lattice-summed calls."""
+    return diamagnetic_map(p, pattern, rho, direction) - paramagnetic_map(p, pattern, D, direction)

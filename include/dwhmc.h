@@ -182,7 +182,7 @@ int dwh_stream(dwh_ctx* ctx, void** stream);
  * (bit 0 "gj_update", bit 1 "gj_pivot", bit 2 "assemble", bit 3 "contract",
  * bit 4 "step", bit 5 "gj_edge", bit 6 "cr_gemm", bit 7 "cr_inv", bit 8 "cr_inv_side",
  * bit 9 "eig_own", bit 10 "eig_vendor", bit 11 "cr_sparse", bit 12 "spectral",
- * bit 13 "response", bit 14 "operator", bit 15 "nambu");
+ * bit 13 "response", bit 14 "operator", bit 15 "nambu", bit 16 "map");
  * 0 disables, -1 times everything. */
 int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
 /* name: "gj_update" (rank-128 paired / rank-64 trailing updates),
@@ -200,7 +200,9 @@ int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
  * state, the J_nm product's), "operator" (the same for
  * dwh_measure_operator_response; work = 8·(2N)³ flops per operator per
  * state), "nambu" (the same for dwh_measure_nambu_response; work = 8·(2N)³
- * flops per vertex per state), "assemble",
+ * flops per vertex per state), "map" (the same for dwh_measure_response_map;
+ * work = 8·(2N)³ flops per vertex, for X, plus 8·(2N)³ per (vertex, frequency),
+ * per state; 0 without a dmap output), "assemble",
  * "contract", "step"; returns total milliseconds, launches and the
  * algorithmic work summed over launches (fp64 flops; HBM bytes for
  * "assemble"). */
@@ -487,6 +489,82 @@ int dwh_measure_nambu_response(dwh_ctx* ctx, int64_t chain, int64_t nstates, con
 int dwh_debug_nambu_dense(int64_t N, int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
                           const dwh_c128* val, int64_t npairs, const int64_t* pairs, dwh_c128* out);
 
+/* ---- response maps: δρ(z)[W] and ρ on any site / bond pattern --------------
+ * Where the responses above are lattice sums, this returns the matrix behind
+ * them at the entries a caller names: the linear-response density matrix of a
+ * source vertex W (a Nambu vertex, as in dwh_measure_nambu_response) at a
+ * frequency z,
+ *   D(z)[W] = U (w(z) ∘ U^H W U) U^H,
+ * and the equal-time ρ = U f U^H, both only on a pattern of npat Nambu index
+ * pairs (a_e, b_e) = (prow[e], pcol[e]) in [0, 2N): sites (a = b), bonds, any
+ * block.  Any order, duplicates allowed (each gets its own value), outputs in
+ * the caller's order, no 1/N applied:
+ *   dmap[e + npat·(z + nz·(k + nops·s))] = Σ_nm U[a_e,n] w_nm(z) X^k_nm conj(U[b_e,m])
+ *   rho [e + npat·s]                     = Σ_n  U[a_e,n] f_n conj(U[b_e,n])
+ * with X^k = U^H W_k U, ΔE_nm = E_m - E_n, f_n = logistic(-β E_n) and
+ * z over nz = n_matsubara + n_w points, Matsubara first:
+ *   Matsubara l:  w_nm = r_nm(l) + i s_nm(l) exactly as in
+ *                 dwh_measure_nambu_response (the l = 0 rule β f_n (1 - f_n)
+ *                 where |ΔE| < 1e-8 included);
+ *   retarded ω_j = omega[j], of either sign:  w_nm = (f_n - f_m)/(ΔE_nm - ω_j - iη),
+ *                 0 where |f_n - f_m| < 1e-12 (the rule of χ''); eta > 0.
+ * Every response of the calls above is a contraction: for a vertex B whose
+ * entries lie in the pattern, Σ_e conj(B_e) D_e = N·chi of the pair (W, B),
+ * its imaginary part at ω + iη N·chi2 for B = W; D(l = 0)[W] = -∂ρ/∂ε under
+ * H → H + εW for Hermitian W; Tr D(l >= 1) = 0.  ρ gives the local density,
+ * the bond kinetic energy (so the local diamagnetic term) and P_ij =
+ * -ρ[i, j+N] - ρ[j, i+N] (vertices.py: bond_pattern, contract and the local
+ * stiffness maps).
+ * Vertices, Delta / nstates / chain, every algorithm, one eigensolve per state
+ * and "the context's own Δ is not touched" as in dwh_measure_nambu_response.
+ * Either output may be NULL, which skips that part (without dmap no vertex is
+ * applied and n_matsubara + n_w may be 0).
+ * Cost per (vertex, frequency) and state: one more 2N-cubed product on the
+ * library's own MFMA kernel, S_z = K_z U^H with K_z = w(z) ∘ X (so that both
+ * operands of the sampled product D_e = Σ_n conj(U^H[n, a_e]) S_z[n, b_e] are
+ * contiguous columns), then the sampled product over the pattern grouped by b
+ * (a workgroup stages column b of S_z in LDS and takes 32 entries of it;
+ * dwhmc_map.hip); ρ the same on S = diag(f) U^H with no product.  Each real
+ * frequency costs a product, hence a list and not a grid.  Workspace: the
+ * vertices run in the groups of the current response (at most 2 GiB,
+ * DWHMC_RESPONSE_GROUP=g lowers them) and the frequencies of one vertex in
+ * chunks whose K_z and S_z take at most 2 GiB more (2·chunk·(2N)² complex;
+ * one frequency is always allowed, at most 64 per chunk; DWHMC_MAP_CHUNK=c
+ * lowers it) with chunk·npat sampled entries (at most 1 GiB); allocated on
+ * first use, grown on demand, freed with the other response workspaces.
+ * Every sum has a fixed order: two calls give the same bits, a batch of
+ * snapshots equals its single-state calls, smaller groups and chunks give the
+ * same bits.
+ * DWH_ERR_ARG, nothing launched: every case dwh_measure_nambu_response refuses
+ * for its vertices and states, rho and dmap both NULL, npat < 1 or > 2^24, a
+ * pattern index outside [0, 2N), NULL prow / pcol, a negative count, more than
+ * 2^16 frequencies of a kind or 2^20 (vertex, frequency) points, no frequency
+ * with a dmap output, NULL omega with n_w > 0, a non-finite or non-positive
+ * eta with n_w > 0, a non-finite ω, 2N > 8192 (the staged column). */
+int dwh_measure_response_map(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta,
+                             int64_t nops, const int64_t* rowptr, const int64_t* col, int64_t nnz,
+                             const dwh_c128* val, int64_t npat, const int64_t* prow, const int64_t* pcol,
+                             int64_t n_matsubara, double eta, int64_t n_w, const double* omega,
+                             dwh_c128* rho, dwh_c128* dmap);
+/* Host only (no device, no context): the validation of the pattern above and
+ * the column-grouped ordering the sampled product consumes.  order (npat): a
+ * permutation of the entries sorted by b = pcol, stable inside a column;
+ * colptr (2N + 1): the entries of column b are order[colptr[b]] ..
+ * order[colptr[b+1] - 1].  Errors as above, the text where
+ * dwh_last_error(NULL) reads it. */
+int dwh_debug_response_map_plan(int64_t N, int64_t npat, const int64_t* prow, const int64_t* pcol,
+                                int64_t* order, int64_t* colptr);
+/* Bench (tools/bench_response_map.py): the two stages around the product of
+ * dwh_measure_response_map alone — the weight kernel for nfreq frequencies of
+ * one vertex, and the sampled product of nfreq matrices on the last call's
+ * pattern — on the buffers as the last call with a dmap output left them,
+ * each reps times back to back after one warm-up launch, HIP-event timed;
+ * milliseconds per launch.  nfreq at most that call's frequencies per chunk.
+ * Overwrites that call's K_z and sampled-entry buffers.  DWH_ERR_STATE before
+ * such a call. */
+int dwh_bench_response_map_stages(dwh_ctx* ctx, int64_t reps, int64_t nfreq, double* weight_ms,
+                                  double* sample_ms);
+
 /* ---- assembly read-back (parity tests; not on the hot path) -------------
  * The BdG matrix H_BdG(Δ) exactly as the device assembles it, so tests can
  * compare it bit-for-bit with init_static_H! + update_H_BdG!
@@ -517,8 +595,8 @@ int dwh_debug_qeig(dwh_ctx* ctx, int64_t chain, double* E, double* ms);
  * (U need not diagonalise anything).  The next eigensolve of this context
  * with exactly nstates matrices — the one dwh_measure_transport(_deltas),
  * dwh_measure_spectral_maps, dwh_measure_current_response,
- * dwh_measure_operator_response and dwh_measure_nambu_response run after
- * preparing their buffers — copies
+ * dwh_measure_operator_response, dwh_measure_nambu_response and
+ * dwh_measure_response_map run after preparing their buffers — copies
  * them into its slots instead of solving, reports the solve as particle-hole
  * closed (dwh_info_t::eig_half) iff ph != 0 and as not structure-preserving
  * (eig_quat = 0), and clears the staging: the injection is one-shot.  With

@@ -300,6 +300,41 @@ function measure_nambu_response(cache::GPUCache, p::ModelParameters, rowptr::Vec
     return χ, χ2
 end
 
+# Response maps for the Δ the context holds (dwh_measure_response_map): the
+# linear-response density matrix D(z)[W_k] = U (w(z) ∘ Uᴴ W_k U) Uᴴ of every
+# source vertex (the CSR form of measure_nambu_response) and the equal-time
+# ρ = U f Uᴴ, at the Nambu index pairs `pattern[:, e]` = (a_e, b_e), 0-based in
+# [0, 2N), any order, duplicates allowed.  z runs over the n_matsubara
+# Matsubara indices, then the real frequencies `ω` (w = (f_n - f_m)/(ΔE - ω -
+# iη); needs η > 0).  Returns (ρ, D): ρ[e + 1] and D[e + 1, z + 1, k + 1], both
+# complex, no 1/N applied; Σ_e conj(B_e) D_e = N·χ of measure_nambu_response
+# for the pair (W_k, B).  `rho = false` skips ρ (returned empty), no frequency
+# at all skips D.  Not run; the same ABI call is exercised through
+# ctypes by tests/test_response_map.py.
+function measure_response_map(cache::GPUCache, p::ModelParameters, rowptr::Vector{Int64},
+                              col::Vector{Int64}, val::Matrix{ComplexF64}, pattern::Matrix{Int64};
+                              n_matsubara::Integer=1, η::Real=p.η, ω::Vector{Float64}=Float64[],
+                              rho::Bool=true)
+    nnz, nops = size(val)
+    length(col) == nnz || throw(ArgumentError("val must be nnz x nops with nnz = length(col)"))
+    length(rowptr) == 2 * p.N + 1 || throw(ArgumentError("rowptr must have 2N + 1 entries"))
+    size(pattern, 1) == 2 || throw(ArgumentError("pattern must be 2 x npat"))
+    npat = size(pattern, 2)
+    prow, pcol = pattern[1, :], pattern[2, :]
+    n_ω = length(ω)
+    nz = max(n_matsubara, 0) + n_ω
+    ρ = zeros(ComplexF64, rho ? npat : 0)
+    D = zeros(ComplexF64, npat, nz, nz > 0 ? nops : 0)
+    GC.@preserve rowptr col val prow pcol ω ρ D check(cache.ctx, ccall((:dwh_measure_response_map, libdwhmc), Cint,
+                           (Ptr{Cvoid}, Int64, Int64, Ptr{ComplexF64}, Int64, Ptr{Int64}, Ptr{Int64}, Int64,
+                            Ptr{ComplexF64}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Float64, Int64, Ptr{Float64},
+                            Ptr{ComplexF64}, Ptr{ComplexF64}),
+                           cache.ctx, 0, 1, C_NULL, nops, pointer(rowptr), pointer(col), nnz, pointer(val),
+                           npat, pointer(prow), pointer(pcol), n_matsubara, Float64(η), n_ω,
+                           n_ω > 0 ? pointer(ω) : C_NULL, rho ? pointer(ρ) : C_NULL, nz > 0 ? pointer(D) : C_NULL))
+    return ρ, D
+end
+
 # ---------------------------------------------------------------------------
 # run_simulation on the GPU.  The reference constructs its cache inside the
 # driver (`cache = initialize_cache(p)`, src/Simulation.jl:82), so the driver
