@@ -209,60 +209,44 @@ class FermionContext:
         """measure_transport_and_spectra (src/Observables.jl:314-526) for one
         chain at the device Δ; keys are the SpectrumResult fields
         (:293-308), A_k_omega0 indexed [kx, ky]."""
-        nw, nd = transport_grid(eta, domega, omega_max, self._lib)
-        Lx, Ly = self.info_lattice
-        st, dc = C.c_double(), C.c_double()
-        sigma, dos, dos_an = np.empty(nw), np.empty(nd), np.empty(nd)
-        ak = np.empty(Lx * Ly)
-        self._c(self._lib.dwh_measure_transport(self._h, int(chain), float(eta), float(domega),
-                                                float(omega_max), C.byref(st), C.byref(dc), ptr(sigma),
-                                                nw, ptr(dos), ptr(dos_an), nd, ptr(ak)))
-        return dict(superfluid_stiffness=st.value, dc_conductivity=dc.value,
-                    omega_grid=eta + domega * np.arange(nw), optical_conductivity=sigma,
-                    dos_omega_grid=-omega_max + domega * np.arange(nd), dos=dos, dos_AN=dos_an,
-                    A_k_omega0=ak.reshape(Ly, Lx).T.copy())
+        o = _TransportOutputs(self, 1, eta, domega, omega_max)
+        dp = C.POINTER(C.c_double)                       # (this entry declares its two scalars as double*)
+        self._c(self._lib.dwh_measure_transport(self._h, int(chain), float(eta), float(domega), float(omega_max),
+                                                o.st.ctypes.data_as(dp), o.dc.ctypes.data_as(dp), ptr(o.sigma),
+                                                o.nw, ptr(o.dos), ptr(o.dos_an), o.nd, ptr(o.ak)))
+        return o.results()[0]
 
     def measure_transport_all(self, eta: float, domega: float, omega_max: float) -> list:
         """measure_transport for every chain, the eigensolves and J_mn
         products batched (dwh_measure_transport_batched); one dict per chain."""
-        nw, nd = transport_grid(eta, domega, omega_max, self._lib)
-        Lx, Ly = self.info_lattice
-        nc = self.nchains
-        st, dc = np.empty(nc), np.empty(nc)
-        sigma, dos, dos_an = np.empty((nc, nw)), np.empty((nc, nd)), np.empty((nc, nd))
-        ak = np.empty((nc, Lx * Ly))
+        o = _TransportOutputs(self, self.nchains, eta, domega, omega_max)
         self._c(self._lib.dwh_measure_transport_batched(self._h, float(eta), float(domega), float(omega_max),
-                                                        ptr(st), ptr(dc), ptr(sigma), nw, ptr(dos),
-                                                        ptr(dos_an), nd, ptr(ak)))
-        wg, dg = eta + domega * np.arange(nw), -omega_max + domega * np.arange(nd)
-        return [dict(superfluid_stiffness=float(st[c]), dc_conductivity=float(dc[c]), omega_grid=wg.copy(),
-                     optical_conductivity=sigma[c].copy(), dos_omega_grid=dg.copy(), dos=dos[c].copy(),
-                     dos_AN=dos_an[c].copy(), A_k_omega0=ak[c].reshape(Ly, Lx).T.copy())
-                for c in range(nc)]
+                                                        ptr(o.st), ptr(o.dc), ptr(o.sigma), o.nw, ptr(o.dos),
+                                                        ptr(o.dos_an), o.nd, ptr(o.ak)))
+        return o.results()
 
     def measure_transport_deltas(self, deltas, eta: float, domega: float, omega_max: float,
                                  chain: int = 0) -> list:
         """measure_transport at a list of pairing fields (each (N, 2)) on the
         lattice and disorder of `chain`, eigensolves batched over the list
         (dwh_measure_transport_deltas); one dict per field, in order."""
-        D = np.asarray(deltas, dtype=np.complex128)
-        if D.ndim != 3 or D.shape[1:] != (self.N, 2):
-            raise ValueError(f"expected (nstates, {self.N}, 2) pairing fields")
-        ns = D.shape[0]
-        d = np.ascontiguousarray(np.transpose(D, (0, 2, 1)))
-        nw, nd = transport_grid(eta, domega, omega_max, self._lib)
-        Lx, Ly = self.info_lattice
-        st, dc = np.empty(ns), np.empty(ns)
-        sigma, dos, dos_an = np.empty((ns, nw)), np.empty((ns, nd)), np.empty((ns, nd))
-        ak = np.empty((ns, Lx * Ly))
+        ns, d = self._states(deltas, min_states=0)
+        o = _TransportOutputs(self, ns, eta, domega, omega_max)
         self._c(self._lib.dwh_measure_transport_deltas(self._h, int(chain), ns, ptr(d), float(eta), float(domega),
-                                                       float(omega_max), ptr(st), ptr(dc), ptr(sigma), nw,
-                                                       ptr(dos), ptr(dos_an), nd, ptr(ak)))
-        wg, dg = eta + domega * np.arange(nw), -omega_max + domega * np.arange(nd)
-        return [dict(superfluid_stiffness=float(st[k]), dc_conductivity=float(dc[k]), omega_grid=wg.copy(),
-                     optical_conductivity=sigma[k].copy(), dos_omega_grid=dg.copy(), dos=dos[k].copy(),
-                     dos_AN=dos_an[k].copy(), A_k_omega0=ak[k].reshape(Ly, Lx).T.copy())
-                for k in range(ns)]
+                                                       float(omega_max), ptr(o.st), ptr(o.dc), ptr(o.sigma), o.nw,
+                                                       ptr(o.dos), ptr(o.dos_an), o.nd, ptr(o.ak)))
+        return o.results()
+
+    def _states(self, deltas, min_states: int = 1):
+        """(nstates, pairing fields in the ABI layout) of a call's `deltas`
+        ((nstates, N, 2)); None, where a call takes it, is the one state at
+        the device Δ: (1, None)."""
+        if deltas is None and min_states > 0:
+            return 1, None
+        D = np.asarray(deltas, dtype=np.complex128)
+        if D.ndim != 3 or D.shape[1:] != (self.N, 2) or D.shape[0] < min_states:
+            raise ValueError(f"expected (nstates, {self.N}, 2) pairing fields")
+        return D.shape[0], np.ascontiguousarray(np.transpose(D, (0, 2, 1)))
 
     def measure_spectral_maps(self, eta: float, domega: float, omega_max: float, first: int = 0,
                               count: int | None = None, stride: int = 1, chain: int = 0, deltas=None,
@@ -277,13 +261,7 @@ class FermionContext:
         first, stride = int(first), int(stride)
         omega = spectral_window(eta, domega, omega_max, first, count, stride, self._lib)
         count = len(omega)
-        d, ns = None, 1
-        if deltas is not None:
-            D = np.asarray(deltas, dtype=np.complex128)
-            if D.ndim != 3 or D.shape[1:] != (self.N, 2) or D.shape[0] < 1:
-                raise ValueError(f"expected (nstates, {self.N}, 2) pairing fields")
-            ns = D.shape[0]
-            d = np.ascontiguousarray(np.transpose(D, (0, 2, 1)))
+        ns, d = self._states(deltas)
         Lx, Ly = self.info_lattice
         out_l = np.empty((ns, count, Ly, Lx)) if ldos else None
         out_a = np.empty((ns, count, Ly, Lx)) if akw else None
@@ -312,20 +290,12 @@ class FermionContext:
         d = 0 if direction in ("x", 0) else 1
         qa = np.ascontiguousarray(np.asarray(q, dtype=np.int64).reshape(-1, 2))
         nq, nl = qa.shape[0], int(n_matsubara)
-        D, ns = None, 1
-        if deltas is not None:
-            Dl = np.asarray(deltas, dtype=np.complex128)
-            if Dl.ndim != 3 or Dl.shape[1:] != (self.N, 2) or Dl.shape[0] < 1:
-                raise ValueError(f"expected (nstates, {self.N}, 2) pairing fields")
-            ns = Dl.shape[0]
-            D = np.ascontiguousarray(np.transpose(Dl, (0, 2, 1)))
+        ns, D = self._states(deltas)
         dia = np.empty(ns)
         lam = np.empty((ns, max(nq, 0), max(nl, 0)))
         self._c(self._lib.dwh_measure_current_response(self._h, int(chain), ns, ptr(D), d, nq, ptr(qa), nl,
                                                        ptr(dia), ptr(lam)))
-        if deltas is None:
-            return dict(dia=float(dia[0]), lam=lam[0])
-        return dict(dia=dia, lam=lam)
+        return _per_state(deltas, scalars=("dia",), dia=dia, lam=lam)
 
     def measure_operator_response(self, ops, spin_sign=None, n_matsubara: int = 1, omega=None, eta=None,
                                   chain: int = 0, deltas=None) -> dict:
@@ -349,11 +319,7 @@ class FermionContext:
         if isinstance(ops, tuple):
             if len(ops) != 3:
                 raise ValueError("ops: a CSR tuple (rowptr, col, val) or a list of operators")
-            rowptr = np.ascontiguousarray(ops[0], dtype=np.int64).ravel()
-            col = np.ascontiguousarray(ops[1], dtype=np.int64).ravel()
-            val = np.ascontiguousarray(np.atleast_2d(np.asarray(ops[2], dtype=np.complex128)))
-            if len(rowptr) != N + 1 or val.ndim != 2 or val.shape[1] != len(col):
-                raise ValueError(f"ops: rowptr of {N + 1} entries and val (nops, {len(col)}) expected")
+            rowptr, col, val = _csr_tuple(ops, N, "ops: rowptr of {n} entries and val (nops, {nnz}) expected")
         else:
             ops = list(ops)
             if not ops:
@@ -368,34 +334,15 @@ class FermionContext:
             raise ValueError("spin_sign is needed with a CSR tuple")
         sg = np.ascontiguousarray(np.broadcast_to(np.asarray(spin_sign, dtype=np.int32), (nops,)))
         nl = int(n_matsubara)
-        if omega is None:
-            w0, dw, nw = 0.0, 0.0, 0
-        else:
-            if isinstance(omega, dict):
-                extra = set(omega) - {"start", "step", "count"}
-                if extra:
-                    raise ValueError(f"omega: unknown keys {sorted(extra)}")
-                omega = (omega["start"], omega["step"], omega["count"])
-            w0, dw, nw = float(omega[0]), float(omega[1]), int(omega[2])
-            if eta is None:
-                raise ValueError("eta is needed with omega")
-        D, ns = None, 1
-        if deltas is not None:
-            Dl = np.asarray(deltas, dtype=np.complex128)
-            if Dl.ndim != 3 or Dl.shape[1:] != (N, 2) or Dl.shape[0] < 1:
-                raise ValueError(f"expected (nstates, {N}, 2) pairing fields")
-            ns = Dl.shape[0]
-            D = np.ascontiguousarray(np.transpose(Dl, (0, 2, 1)))
+        w0, dw, nw = _omega_grid(omega, eta)
+        ns, D = self._states(deltas)
         chi = np.empty((ns, nops, max(nl, 0)))
         chi2 = np.empty((ns, nops, max(nw, 0)))
         self._c(self._lib.dwh_measure_operator_response(
             self._h, int(chain), ns, ptr(D), nops, ptr(rowptr), ptr(col), nnz, ptr(val), ptr(sg), nl,
             ptr(chi) if nl > 0 else None, 0.0 if eta is None else float(eta), w0, dw, nw,
             ptr(chi2) if nw > 0 else None))
-        grid = w0 + dw * np.arange(max(nw, 0))
-        if deltas is None:
-            return dict(chi=chi[0], chi2=chi2[0], omega=grid)
-        return dict(chi=chi, chi2=chi2, omega=grid)
+        return dict(_per_state(deltas, chi=chi, chi2=chi2), omega=w0 + dw * np.arange(max(nw, 0)))
 
     def measure_nambu_response(self, vertices, pairs=None, n_matsubara: int = 1, omega=None, eta=None,
                                chain: int = 0, deltas=None) -> dict:
@@ -424,34 +371,15 @@ class FermionContext:
         pr = np.ascontiguousarray(pr)
         npairs = pr.shape[0]
         nl = int(n_matsubara)
-        if omega is None:
-            w0, dw, nw = 0.0, 0.0, 0
-        else:
-            if isinstance(omega, dict):
-                extra = set(omega) - {"start", "step", "count"}
-                if extra:
-                    raise ValueError(f"omega: unknown keys {sorted(extra)}")
-                omega = (omega["start"], omega["step"], omega["count"])
-            w0, dw, nw = float(omega[0]), float(omega[1]), int(omega[2])
-            if eta is None:
-                raise ValueError("eta is needed with omega")
-        D, ns = None, 1
-        if deltas is not None:
-            Dl = np.asarray(deltas, dtype=np.complex128)
-            if Dl.ndim != 3 or Dl.shape[1:] != (N, 2) or Dl.shape[0] < 1:
-                raise ValueError(f"expected (nstates, {N}, 2) pairing fields")
-            ns = Dl.shape[0]
-            D = np.ascontiguousarray(np.transpose(Dl, (0, 2, 1)))
+        w0, dw, nw = _omega_grid(omega, eta)
+        ns, D = self._states(deltas)
         chi = np.empty((ns, npairs, max(nl, 0)), dtype=np.complex128)
         chi2 = np.empty((ns, npairs, max(nw, 0)), dtype=np.complex128)
         self._c(self._lib.dwh_measure_nambu_response(
             self._h, int(chain), ns, ptr(D), nops, ptr(rowptr), ptr(col), nnz, ptr(val), npairs, ptr(pr), nl,
             ptr(chi) if nl > 0 else None, 0.0 if eta is None else float(eta), w0, dw, nw,
             ptr(chi2) if nw > 0 else None))
-        grid = w0 + dw * np.arange(max(nw, 0))
-        if deltas is None:
-            return dict(chi=chi[0], chi2=chi2[0], omega=grid, pairs=pr)
-        return dict(chi=chi, chi2=chi2, omega=grid, pairs=pr)
+        return dict(_per_state(deltas, chi=chi, chi2=chi2), omega=w0 + dw * np.arange(max(nw, 0)), pairs=pr)
 
     def measure_response_map(self, vertices, pattern, n_matsubara: int = 1, omega=None, eta=None, rho: bool = True,
                              chain: int = 0, deltas=None) -> dict:
@@ -484,21 +412,13 @@ class FermionContext:
         if nw > 0 and eta is None:
             raise ValueError("eta is needed with omega")
         nz = max(nl, 0) + nw
-        D, ns = None, 1
-        if deltas is not None:
-            Dl = np.asarray(deltas, dtype=np.complex128)
-            if Dl.ndim != 3 or Dl.shape[1:] != (N, 2) or Dl.shape[0] < 1:
-                raise ValueError(f"expected (nstates, {N}, 2) pairing fields")
-            ns = Dl.shape[0]
-            D = np.ascontiguousarray(np.transpose(Dl, (0, 2, 1)))
+        ns, D = self._states(deltas)
         dmap = np.empty((ns, nops, nz, npat), dtype=np.complex128) if nz > 0 else None
         r = np.empty((ns, npat), dtype=np.complex128) if rho else None
         self._c(self._lib.dwh_measure_response_map(
             self._h, int(chain), ns, ptr(D), nops, ptr(rowptr), ptr(col), nnz, ptr(val), npat, ptr(prow), ptr(pcol),
             nl, 0.0 if eta is None else float(eta), nw, ptr(w) if nw > 0 else None, ptr(r), ptr(dmap)))
-        if deltas is None:
-            dmap, r = (None if dmap is None else dmap[0]), (None if r is None else r[0])
-        return dict(dmap=dmap, rho=r, pattern=pat, omega=w)
+        return dict(_per_state(deltas, dmap=dmap, rho=r), pattern=pat, omega=w)
 
     # -- assembly read-back (parity tests) --------------------------------
     def debug_dense_H(self, chain: int = 0) -> np.ndarray:
@@ -605,16 +525,70 @@ def _nambu_csr(vx, vertices, N: int):
     first = vertices[0] if isinstance(vertices, tuple) and len(vertices) == 3 else None
     if first is not None and not isinstance(first, (tuple, list)) and np.ndim(first) == 1 \
             and len(first) == 2 * N + 1 and np.issubdtype(np.asarray(first).dtype, np.integer):
-        rowptr = np.ascontiguousarray(vertices[0], dtype=np.int64).ravel()
-        col = np.ascontiguousarray(vertices[1], dtype=np.int64).ravel()
-        val = np.ascontiguousarray(np.atleast_2d(np.asarray(vertices[2], dtype=np.complex128)))
-        if val.ndim != 2 or val.shape[1] != len(col):
-            raise ValueError(f"vertices: a CSR tuple needs val (nops, {len(col)})")
-        return rowptr, col, val
+        return _csr_tuple(vertices, 2 * N, "vertices: a CSR tuple needs val (nops, {nnz})")
     vertices = list(vertices)
     if not vertices:
         raise ValueError("vertices is empty")
     return vx.union_csr_nambu(vertices, N)
+
+
+def _csr_tuple(csr, nrows: int, message: str):
+    """(rowptr, col, val (nops, nnz)) of a CSR tuple over nrows rows as the ABI
+    takes them: contiguous int64, int64 and complex128.  message: the caller's
+    ValueError text for a wrong shape ({n}: nrows + 1, {nnz}: len(col))."""
+    rowptr = np.ascontiguousarray(csr[0], dtype=np.int64).ravel()
+    col = np.ascontiguousarray(csr[1], dtype=np.int64).ravel()
+    val = np.ascontiguousarray(np.atleast_2d(np.asarray(csr[2], dtype=np.complex128)))
+    if len(rowptr) != nrows + 1 or val.ndim != 2 or val.shape[1] != len(col):
+        raise ValueError(message.format(n=nrows + 1, nnz=len(col)))
+    return rowptr, col, val
+
+
+def _omega_grid(omega, eta):
+    """(start, step, count) of a call's real-frequency grid: None (no grid: 0
+    points), dict(start=, step=, count=) or (start, step, count); it needs eta."""
+    if omega is None:
+        return 0.0, 0.0, 0
+    if isinstance(omega, dict):
+        extra = set(omega) - {"start", "step", "count"}
+        if extra:
+            raise ValueError(f"omega: unknown keys {sorted(extra)}")
+        omega = (omega["start"], omega["step"], omega["count"])
+    grid = float(omega[0]), float(omega[1]), int(omega[2])
+    if eta is None:
+        raise ValueError("eta is needed with omega")
+    return grid
+
+
+def _per_state(deltas, scalars=(), **arrays) -> dict:
+    """A call's (nstates, ...) results as it returns them: as they are with
+    `deltas`, else (the one state at the device Δ) without the state axis,
+    those named in `scalars` as floats."""
+    if deltas is not None:
+        return arrays
+    return {k: a if a is None else float(a[0]) if k in scalars else a[0] for k, a in arrays.items()}
+
+
+class _TransportOutputs:
+    """The output arrays of a transport call for ns states (st, dc (ns,);
+    sigma (ns, nw); dos, dos_an (ns, nd); ak (ns, N)) and, after the call,
+    its result dicts."""
+
+    def __init__(self, ctx, ns: int, eta, domega, omega_max):
+        self.nw, self.nd = transport_grid(eta, domega, omega_max, ctx._lib)
+        self.Lx, self.Ly = ctx.info_lattice
+        self.grids = eta + domega * np.arange(self.nw), -omega_max + domega * np.arange(self.nd)
+        self.st, self.dc = np.empty(ns), np.empty(ns)
+        self.sigma, self.dos, self.dos_an = np.empty((ns, self.nw)), np.empty((ns, self.nd)), np.empty((ns, self.nd))
+        self.ak = np.empty((ns, self.Lx * self.Ly))
+
+    def results(self) -> list:
+        """One dict per state, keys the SpectrumResult fields; every dict owns its arrays."""
+        wg, dg = self.grids
+        return [dict(superfluid_stiffness=float(self.st[k]), dc_conductivity=float(self.dc[k]), omega_grid=wg.copy(),
+                     optical_conductivity=self.sigma[k].copy(), dos_omega_grid=dg.copy(), dos=self.dos[k].copy(),
+                     dos_AN=self.dos_an[k].copy(), A_k_omega0=self.ak[k].reshape(self.Ly, self.Lx).T.copy())
+                for k in range(len(self.st))]
 
 
 def transport_grid(eta: float, domega: float, omega_max: float, lib=None):

@@ -79,8 +79,246 @@ def transport_csv_line(sweep: int, spec) -> str:
     return "%d,%.6f,%.6f\n" % (sweep, spec.superfluid_stiffness, spec.dc_conductivity)
 
 
-def write_spectra_header(spec_dir: str, p) -> None:
-    """jldsave(params, omega_grid) of src/Simulation.jl:89."""
+class _Option:
+    """One measurement option of the drivers: what run_simulation,
+    run_simulation_chains and TransportQueue need to know about one of their
+    keywords, parsed once from the user's dict (ValueError for what it
+    refuses).  Every option is a dict whose entries are each optional, or None
+    (the default): not taken, every file as without it.  With it, every
+    transport measurement also makes the option's one FermionContext call, at
+    the device Δ or batched over a TransportQueue's Δ snapshots.
+
+    keyword    the drivers' keyword
+    keys       the entries the dict may hold
+    header     None, or (file name, array): the file written under
+               spectra_bins/ before the run (write_headers)
+    csv_file   None, or the CSV file that gets one row per measurement:
+               sweep, then csv_values as %.12e under csv_columns
+    measure    the FermionContext call; every result with the leading state
+               axis, one state at the device Δ when deltas is None
+    bins       the entries of state k for sweep_<i>.npz (their bin means are
+               written, SpectraBins)"""
+    keyword, keys, header, csv_file = None, (), None, None
+    squeezed = ()        # result entries that FermionContext returns without the state axis at deltas=None
+
+    def __init__(self, raw: dict, p):
+        extra = set(raw) - set(self.keys)
+        if extra:
+            raise ValueError(f"{self.keyword}: unknown keys {sorted(extra)}")
+
+    def _vertex_names(self, raw: dict, key: str, default) -> list:
+        names = [(str(kind), (int(m[0]), int(m[1]))) for kind, m in raw.get(key, [default])]
+        if not names:
+            raise ValueError(f"{self.keyword}: {key} is empty")
+        return names
+
+    def _frequencies(self, raw: dict, p, omega, what: str):
+        """n_matsubara, omega (None when empty) and eta (default: the run's)"""
+        nl = int(raw.get("n_matsubara", 1))
+        if nl < 0 or (nl == 0 and not omega):
+            raise ValueError(f"{self.keyword}: n_matsubara >= 0, and {what} when it is 0")
+        self.n_matsubara, self.omega, self.eta = nl, omega or None, float(raw.get("eta", p.eta))
+
+    def measure(self, ctx, p, chain: int, deltas) -> dict:
+        r = self._call(ctx, p, chain, deltas)
+        if deltas is None:
+            r = dict(r, **{k: np.asarray(r[k])[None] for k in self.squeezed})
+        return r
+
+    def bins(self, r: dict, k: int) -> dict:
+        return {}
+
+
+class SpectralMaps(_Option):
+    """spectral_maps = dict(first=, count=, stride=): LDOS(i, ω) and A(k, ω)
+    on the window first + q·stride, q < count, of the DOS grid (count None: to
+    its end; FermionContext.measure_spectral_maps).  Each sweep_<i>.npz gains
+    the bin means ldos and akw ((count, Ly, Lx));
+    spectra_bins/maps_omega.npy holds the window's frequencies."""
+    keyword, keys = "spectral_maps", ("first", "count", "stride")
+
+    def __init__(self, raw, p):
+        super().__init__(raw, p)
+        self.window = dict(first=raw.get("first", 0), count=raw.get("count"), stride=raw.get("stride", 1))
+        self.header = ("maps_omega.npy", spectral_window(p.eta, p.domega, p.omega_max, **self.window))
+
+    def _call(self, ctx, p, chain, deltas):
+        return ctx.measure_spectral_maps(p.eta, p.domega, p.omega_max, chain=chain, deltas=deltas, **self.window)
+
+    def bins(self, r, k):
+        return {"ldos": r["ldos"][k], "akw": r["akw"][k]}
+
+
+class CurrentResponse(_Option):
+    """current_response = dict(direction=, q=[(mx, my), ...], n_matsubara=)
+    (defaults "x", [(0, 1)], 1; FermionContext.measure_current_response):
+    current_response.csv gets sweep, dia, then Λ(q, iΩ_l) in the ABI order
+    (momentum by momentum, l fastest), the columns named by direction,
+    momentum indices and Matsubara index."""
+    keyword, keys = "current_response", ("direction", "q", "n_matsubara")
+    csv_file, squeezed = "current_response.csv", ("dia", "lam")
+
+    def __init__(self, raw, p):
+        super().__init__(raw, p)
+        self.args = dict(direction=raw.get("direction", "x"),
+                         q=[(int(mx), int(my)) for mx, my in raw.get("q", [(0, 1)])],
+                         n_matsubara=int(raw.get("n_matsubara", 1)))
+
+    def _call(self, ctx, p, chain, deltas):
+        return ctx.measure_current_response(chain=chain, deltas=deltas, **self.args)
+
+    def csv_columns(self):
+        a = self.args["direction"] if isinstance(self.args["direction"], str) else "xy"[self.args["direction"]]
+        return [f"dia_{a}"] + [f"lam_{a}{a}(mx={mx};my={my};l={l})" for mx, my in self.args["q"]
+                               for l in range(self.args["n_matsubara"])]
+
+    def csv_values(self, r, k):
+        return [r["dia"][k], *np.asarray(r["lam"][k]).ravel()]
+
+
+class _GridResponse(_Option):
+    """What operator_response and nambu_response share: n_matsubara (default
+    1; 0 with an omega grid skips the CSV file), omega = dict(start=, step=,
+    count=) (default None: no chi2) and eta (default the run's).  With a grid
+    each sweep_<i>.npz gains the bin mean of chi2 under bins_key and
+    spectra_bins/<grid_file> holds the grid."""
+    squeezed = ("chi", "chi2")
+    grid_file = bins_key = None
+
+    def _grid_frequencies(self, raw, p):
+        omega = raw.get("omega")
+        if omega is not None:
+            if set(omega) != {"start", "step", "count"}:
+                raise ValueError(f"{self.keyword}: omega needs exactly start, step and count")
+            omega = (float(omega["start"]), float(omega["step"]), int(omega["count"]))
+        self._frequencies(raw, p, omega, "an omega grid")
+        if omega is not None:
+            self.header = (self.grid_file, omega[0] + omega[1] * np.arange(omega[2]))
+        if self.n_matsubara >= 1:
+            self.csv_file = self.keyword + ".csv"
+
+    def bins(self, r, k):
+        return {} if self.omega is None else {self.bins_key: r["chi2"][k]}
+
+    def csv_values(self, r, k):
+        return np.ascontiguousarray(r["chi"][k]).ravel().view(np.float64)     # (complex: re, im)
+
+
+class OperatorResponse(_GridResponse):
+    """operator_response = dict(ops=[(kind, (mx, my)), ...], n_matsubara=,
+    omega=, eta=) (kind a key of vertices.KINDS, default the q = 0 density;
+    the vertices are built once, vertices.build;
+    FermionContext.measure_operator_response): operator_response.csv gets
+    sweep, then χ(iΩ_l) operator by operator, l fastest, named by kind,
+    momentum and l; χ''(ω) goes to the bins as chi2 ((nops, count)), its grid
+    to chi2_omega.npy."""
+    keyword, keys = "operator_response", ("ops", "n_matsubara", "omega", "eta")
+    grid_file, bins_key = "chi2_omega.npy", "chi2"
+
+    def __init__(self, raw, p):
+        super().__init__(raw, p)
+        self.names = self._vertex_names(raw, "ops", ("density", (0, 0)))
+        self.ops = [VX.build(kind, p, mx, my) for kind, (mx, my) in self.names]
+        self.spin_sign = [v.spin_sign for v in self.ops]
+        self._grid_frequencies(raw, p)
+
+    def _call(self, ctx, p, chain, deltas):
+        return ctx.measure_operator_response(self.ops, self.spin_sign, n_matsubara=self.n_matsubara,
+                                             omega=self.omega, eta=self.eta, chain=chain, deltas=deltas)
+
+    def csv_columns(self):
+        return [f"chi_{kind}(mx={mx};my={my};l={l})" for kind, (mx, my) in self.names
+                for l in range(self.n_matsubara)]
+
+
+class NambuResponse(_GridResponse):
+    """nambu_response = dict(vertices=[(kind, (mx, my)), ...], pairs=[(a, b),
+    ...], n_matsubara=, omega=, eta=) (kind a key of vertices.NAMBU_KINDS,
+    default the q = 0 pair_d_create, built once by vertices.build_nambu; pairs
+    indices into vertices, default every (k, k);
+    FermionContext.measure_nambu_response): nambu_response.csv gets sweep,
+    then re and im of chi pair by pair, l fastest, named by the pair's two
+    vertices (kind and momentum) and l; the complex chi2 goes to the bins as
+    nambu_chi2 ((npairs, count)), its grid to nambu_chi2_omega.npy."""
+    keyword, keys = "nambu_response", ("vertices", "pairs", "n_matsubara", "omega", "eta")
+    grid_file, bins_key = "nambu_chi2_omega.npy", "nambu_chi2"
+
+    def __init__(self, raw, p):
+        super().__init__(raw, p)
+        self.names = self._vertex_names(raw, "vertices", ("pair_d_create", (0, 0)))
+        self.vertices = [VX.build_nambu(kind, p, mx, my) for kind, (mx, my) in self.names]
+        n, pairs = len(self.names), raw.get("pairs")
+        self.pairs = [(k, k) for k in range(n)] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+        if not self.pairs or any(not (0 <= a < n and 0 <= b < n) for a, b in self.pairs):
+            raise ValueError("nambu_response: pairs must be a non-empty list of vertex index pairs")
+        self._grid_frequencies(raw, p)
+
+    def _call(self, ctx, p, chain, deltas):
+        return ctx.measure_nambu_response(self.vertices, self.pairs, n_matsubara=self.n_matsubara,
+                                          omega=self.omega, eta=self.eta, chain=chain, deltas=deltas)
+
+    def csv_columns(self):
+        def nm(k):
+            kind, (mx, my) = self.names[k]
+            return f"{kind}[mx={mx};my={my}]"
+        return [f"{part}_chi({nm(a)}|{nm(b)};l={l})" for a, b in self.pairs
+                for l in range(self.n_matsubara) for part in ("re", "im")]
+
+
+class ResponseMap(_Option):
+    """response_map = dict(vertices=[(kind, (mx, my)), ...], pattern=,
+    n_matsubara=, omega=[ω, ...], eta=) (kind a key of vertices.NAMBU_KINDS,
+    default the q = 0 current_x; pattern dict(ranges=, blocks=) for
+    vertices.bond_pattern, default all of it, or an (npat, 2) integer array;
+    omega a list of real frequencies, default None; eta default the run's;
+    FermionContext.measure_response_map): the linear-response density matrix
+    of each source vertex and ρ on the pattern.  Each sweep_<i>.npz gains
+    their complex bin means response_map ((nops, nz, npat)) and rho_map
+    ((npat,)); spectra_bins/response_map_pattern.npy holds the pattern."""
+    keyword, keys = "response_map", ("vertices", "pattern", "n_matsubara", "omega", "eta")
+    squeezed = ("dmap", "rho")
+
+    def __init__(self, raw, p):
+        super().__init__(raw, p)
+        self.names = self._vertex_names(raw, "vertices", ("current_x", (0, 0)))
+        self.vertices = [VX.build_nambu(kind, p, mx, my) for kind, (mx, my) in self.names]
+        pattern = raw.get("pattern")
+        if pattern is None or isinstance(pattern, dict):
+            bad = set(pattern or {}) - {"ranges", "blocks"}
+            if bad:
+                raise ValueError(f"response_map: unknown pattern keys {sorted(bad)}")
+            pattern = VX.bond_pattern(p, **(pattern or {}))
+        pattern = np.asarray(pattern)
+        if pattern.ndim != 2 or pattern.shape[1] != 2 or len(pattern) < 1 \
+                or not np.issubdtype(pattern.dtype, np.integer) or pattern.min() < 0 or pattern.max() >= 2 * p.N:
+            raise ValueError("response_map: pattern must be a non-empty (npat, 2) integer array of indices in [0, 2N)")
+        self.pattern = np.ascontiguousarray(pattern, dtype=np.int64)
+        self.header = ("response_map_pattern.npy", self.pattern)
+        omega = raw.get("omega")
+        self._frequencies(raw, p, None if omega is None else [float(w) for w in omega], "a list of frequencies")
+
+    def _call(self, ctx, p, chain, deltas):
+        return ctx.measure_response_map(self.vertices, self.pattern, n_matsubara=self.n_matsubara,
+                                        omega=self.omega, eta=self.eta, chain=chain, deltas=deltas)
+
+    def bins(self, r, k):
+        return {"response_map": r["dmap"][k], "rho_map": r["rho"][k]}
+
+
+# The drivers' measurement options, in the order of their results in the bins.  A further one is a
+# description here and its keyword in the drivers' and TransportQueue's signatures.
+OPTIONS = (SpectralMaps, CurrentResponse, OperatorResponse, NambuResponse, ResponseMap)
+
+
+def parse_options(p, **raw) -> list:
+    """The options taken (not None) among the drivers' keywords, parsed, in the
+    order of OPTIONS."""
+    return [o(raw[o.keyword], p) for o in OPTIONS if raw.get(o.keyword) is not None]
+
+
+def write_headers(spec_dir: str, p, options=()) -> None:
+    """jldsave(params, omega_grid) of src/Simulation.jl:89 as params.json and
+    omega_grid.npy, and the options' header files."""
     os.makedirs(spec_dir, exist_ok=True)
     params = {k: getattr(p, k) for k in ("Lx", "Ly", "t", "tp", "mu", "W", "n_imp", "beta", "J", "mass",
                                          "eta", "domega", "omega_max")}
@@ -88,192 +326,9 @@ def write_spectra_header(spec_dir: str, p) -> None:
         json.dump(params, f, indent=1)
     n, _ = transport_grid(p.eta, p.domega, p.omega_max)
     np.save(os.path.join(spec_dir, "omega_grid.npy"), p.eta + p.domega * np.arange(n))
-
-
-def write_maps_header(spec_dir: str, p, spectral_maps: dict) -> None:
-    """maps_omega.npy: the frequencies of the spectral-maps window."""
-    os.makedirs(spec_dir, exist_ok=True)
-    np.save(os.path.join(spec_dir, "maps_omega.npy"),
-            spectral_window(p.eta, p.domega, p.omega_max, **_maps_window(spectral_maps)))
-
-
-def _maps_window(spectral_maps: dict) -> dict:
-    """first / count / stride of a run's `spectral_maps` option."""
-    extra = set(spectral_maps) - {"first", "count", "stride"}
-    if extra:
-        raise ValueError(f"spectral_maps: unknown keys {sorted(extra)}")
-    return dict(first=spectral_maps.get("first", 0), count=spectral_maps.get("count"),
-                stride=spectral_maps.get("stride", 1))
-
-
-def _response_opts(current_response: dict) -> dict:
-    """direction / q / n_matsubara of a run's `current_response` option."""
-    extra = set(current_response) - {"direction", "q", "n_matsubara"}
-    if extra:
-        raise ValueError(f"current_response: unknown keys {sorted(extra)}")
-    q = [(int(mx), int(my)) for mx, my in current_response.get("q", [(0, 1)])]
-    return dict(direction=current_response.get("direction", "x"), q=q,
-                n_matsubara=int(current_response.get("n_matsubara", 1)))
-
-
-def response_csv_header(opts: dict) -> str:
-    """sweep, dia, then Λ in the ABI order (momentum by momentum, l fastest), the
-    columns named by direction, momentum indices and Matsubara index."""
-    a = opts["direction"] if isinstance(opts["direction"], str) else "xy"[opts["direction"]]
-    cols = [f"lam_{a}{a}(mx={mx};my={my};l={l})" for mx, my in opts["q"] for l in range(opts["n_matsubara"])]
-    return ",".join(["sweep", f"dia_{a}"] + cols)
-
-
-def response_csv_line(sweep: int, dia: float, lam) -> str:
-    return ",".join(["%d" % sweep, "%.12e" % dia] + ["%.12e" % v for v in np.asarray(lam).ravel()]) + "\n"
-
-
-def _operator_opts(operator_response: dict, p) -> dict:
-    """ops / n_matsubara / omega / eta of a run's `operator_response` option:
-    the vertices built once (vertices.build), the χ'' grid as (start, step,
-    count) or None, eta defaulting to the run's."""
-    extra = set(operator_response) - {"ops", "n_matsubara", "omega", "eta"}
-    if extra:
-        raise ValueError(f"operator_response: unknown keys {sorted(extra)}")
-    names = [(str(kind), (int(m[0]), int(m[1]))) for kind, m in operator_response.get("ops", [("density", (0, 0))])]
-    if not names:
-        raise ValueError("operator_response: ops is empty")
-    verts = [VX.build(kind, p, mx, my) for kind, (mx, my) in names]
-    omega = operator_response.get("omega")
-    if omega is not None:
-        bad = set(omega) - {"start", "step", "count"}
-        if bad or set(omega) != {"start", "step", "count"}:
-            raise ValueError("operator_response: omega needs exactly start, step and count")
-        omega = (float(omega["start"]), float(omega["step"]), int(omega["count"]))
-    nl = int(operator_response.get("n_matsubara", 1))
-    if nl < 0 or (nl == 0 and omega is None):
-        raise ValueError("operator_response: n_matsubara >= 0, and an omega grid when it is 0")
-    return dict(names=names, ops=verts, spin_sign=[v.spin_sign for v in verts], n_matsubara=nl, omega=omega,
-                eta=float(operator_response.get("eta", p.eta)))
-
-
-def operator_csv_header(opts: dict) -> str:
-    """sweep, then χ operator by operator, l fastest, named by kind, momentum and l."""
-    return ",".join(["sweep"] + [f"chi_{kind}(mx={mx};my={my};l={l})" for kind, (mx, my) in opts["names"]
-                                 for l in range(opts["n_matsubara"])])
-
-
-def operator_csv_line(sweep: int, chi) -> str:
-    return ",".join(["%d" % sweep] + ["%.12e" % v for v in np.asarray(chi).ravel()]) + "\n"
-
-
-class _NambuOpts(dict):
-    """a `nambu_response` option after _nambu_opts parsed it"""
-
-
-def _nambu_opts(nambu_response: dict, p) -> dict:
-    """vertices / pairs / n_matsubara / omega / eta of a run's `nambu_response`
-    option: the vertices built once (vertices.build_nambu), pairs defaulting to
-    every (k, k), the grid as (start, step, count) or None, eta defaulting to
-    the run's.  Options parsed before (the drivers hand theirs to their
-    TransportQueues) are returned as they are."""
-    if isinstance(nambu_response, _NambuOpts):
-        return nambu_response
-    extra = set(nambu_response) - {"vertices", "pairs", "n_matsubara", "omega", "eta"}
-    if extra:
-        raise ValueError(f"nambu_response: unknown keys {sorted(extra)}")
-    names = [(str(kind), (int(m[0]), int(m[1])))
-             for kind, m in nambu_response.get("vertices", [("pair_d_create", (0, 0))])]
-    if not names:
-        raise ValueError("nambu_response: vertices is empty")
-    verts = [VX.build_nambu(kind, p, mx, my) for kind, (mx, my) in names]
-    pairs = nambu_response.get("pairs")
-    pairs = [(k, k) for k in range(len(names))] if pairs is None else [(int(a), int(b)) for a, b in pairs]
-    if not pairs or any(not (0 <= a < len(names) and 0 <= b < len(names)) for a, b in pairs):
-        raise ValueError("nambu_response: pairs must be a non-empty list of vertex index pairs")
-    omega = nambu_response.get("omega")
-    if omega is not None:
-        if set(omega) != {"start", "step", "count"}:
-            raise ValueError("nambu_response: omega needs exactly start, step and count")
-        omega = (float(omega["start"]), float(omega["step"]), int(omega["count"]))
-    nl = int(nambu_response.get("n_matsubara", 1))
-    if nl < 0 or (nl == 0 and omega is None):
-        raise ValueError("nambu_response: n_matsubara >= 0, and an omega grid when it is 0")
-    return _NambuOpts(names=names, vertices=verts, pairs=pairs, n_matsubara=nl, omega=omega,
-                      eta=float(nambu_response.get("eta", p.eta)))
-
-
-class _MapOpts(dict):
-    """a `response_map` option after _map_opts parsed it"""
-
-
-def _map_opts(response_map: dict, p) -> dict:
-    """vertices / pattern / n_matsubara / omega / eta of a run's `response_map`
-    option: the source vertices built once (vertices.build_nambu), the pattern
-    from dict(ranges=, blocks=) (vertices.bond_pattern; None: all of it) or an
-    (npat, 2) integer array, omega a list of real frequencies or None, eta
-    defaulting to the run's.  Options parsed before are returned as they are."""
-    if isinstance(response_map, _MapOpts):
-        return response_map
-    extra = set(response_map) - {"vertices", "pattern", "n_matsubara", "omega", "eta"}
-    if extra:
-        raise ValueError(f"response_map: unknown keys {sorted(extra)}")
-    names = [(str(kind), (int(m[0]), int(m[1])))
-             for kind, m in response_map.get("vertices", [("current_x", (0, 0))])]
-    if not names:
-        raise ValueError("response_map: vertices is empty")
-    verts = [VX.build_nambu(kind, p, mx, my) for kind, (mx, my) in names]
-    pattern = response_map.get("pattern")
-    if pattern is None or isinstance(pattern, dict):
-        bad = set(pattern or {}) - {"ranges", "blocks"}
-        if bad:
-            raise ValueError(f"response_map: unknown pattern keys {sorted(bad)}")
-        pattern = VX.bond_pattern(p, **(pattern or {}))
-    pattern = np.asarray(pattern)
-    if pattern.ndim != 2 or pattern.shape[1] != 2 or len(pattern) < 1 or not np.issubdtype(pattern.dtype, np.integer) \
-            or pattern.min() < 0 or pattern.max() >= 2 * p.N:
-        raise ValueError("response_map: pattern must be a non-empty (npat, 2) integer array of indices in [0, 2N)")
-    omega = response_map.get("omega")
-    omega = None if omega is None else [float(w) for w in omega]
-    nl = int(response_map.get("n_matsubara", 1))
-    if nl < 0 or (nl == 0 and not omega):
-        raise ValueError("response_map: n_matsubara >= 0, and a list of frequencies when it is 0")
-    return _MapOpts(names=names, vertices=verts, pattern=np.ascontiguousarray(pattern, dtype=np.int64),
-                    n_matsubara=nl, omega=omega or None, eta=float(response_map.get("eta", p.eta)))
-
-
-def write_map_header(spec_dir: str, opts: dict) -> None:
-    """response_map_pattern.npy: the (npat, 2) pattern of the response_map option."""
-    os.makedirs(spec_dir, exist_ok=True)
-    np.save(os.path.join(spec_dir, "response_map_pattern.npy"), opts["pattern"])
-
-
-def nambu_csv_header(opts: dict) -> str:
-    """sweep, then re and im of chi pair by pair, l fastest, named by the pair's
-    two vertices (kind and momentum) and l."""
-    def nm(k):
-        kind, (mx, my) = opts["names"][k]
-        return f"{kind}[mx={mx};my={my}]"
-    return ",".join(["sweep"] + [f"{part}_chi({nm(a)}|{nm(b)};l={l})" for a, b in opts["pairs"]
-                                 for l in range(opts["n_matsubara"]) for part in ("re", "im")])
-
-
-def nambu_csv_line(sweep: int, chi) -> str:
-    c = np.asarray(chi, dtype=np.complex128).ravel()
-    return ",".join(["%d" % sweep] + ["%.12e" % v for z in c for v in (z.real, z.imag)]) + "\n"
-
-
-def write_nambu_header(spec_dir: str, opts: dict) -> None:
-    """nambu_chi2_omega.npy: the chi2 grid of the nambu_response option."""
-    if opts["omega"] is None:
-        return
-    os.makedirs(spec_dir, exist_ok=True)
-    w0, dw, nw = opts["omega"]
-    np.save(os.path.join(spec_dir, "nambu_chi2_omega.npy"), w0 + dw * np.arange(nw))
-
-
-def write_chi2_header(spec_dir: str, opts: dict) -> None:
-    """chi2_omega.npy: the χ'' grid of the operator_response option."""
-    if opts["omega"] is None:
-        return
-    os.makedirs(spec_dir, exist_ok=True)
-    w0, dw, nw = opts["omega"]
-    np.save(os.path.join(spec_dir, "chi2_omega.npy"), w0 + dw * np.arange(nw))
+    for o in options:
+        if o.header is not None:
+            np.save(os.path.join(spec_dir, o.header[0]), o.header[1])
 
 
 class SpectraBins:
@@ -334,9 +389,7 @@ class ChainOutput:
         self.f_trans.write(TRANSPORT_HEADER + "\n")
         self.bins = SpectraBins()
         self.out_dir = out_dir
-        self.f_resp = None           # current_response.csv, only with the current_response option
-        self.f_oper = None           # operator_response.csv, only with the operator_response option
-        self.f_nambu = None          # nambu_response.csv, only with the nambu_response option
+        self.csv = {}                # the options' CSV files by name, each opened by its first row
 
     def tee(self, msg: str):
         line = f"[{datetime.now().strftime('%Y-%m-%d %H:%M:%S')}] {msg}"
@@ -361,44 +414,18 @@ class ChainOutput:
         if self.bins.add(spec, maps) >= bin_size:
             self.bins.flush(self.spec_dir, i)
 
-    def response(self, i, opts, dia, lam):
-        """One row of current_response.csv (created, with its header, by the first)."""
-        if self.f_resp is None:
-            self.f_resp = open(os.path.join(self.out_dir, "current_response.csv"), "w")
-            self.f_resp.write(response_csv_header(opts) + "\n")
-        self.f_resp.write(response_csv_line(i, dia, lam))
-        self.f_resp.flush()
-
-    def operator(self, i, opts, chi):
-        """One row of operator_response.csv (created, with its header, by the first)."""
-        if opts["n_matsubara"] < 1:
-            return
-        if self.f_oper is None:
-            self.f_oper = open(os.path.join(self.out_dir, "operator_response.csv"), "w")
-            self.f_oper.write(operator_csv_header(opts) + "\n")
-        self.f_oper.write(operator_csv_line(i, chi))
-        self.f_oper.flush()
-
-    def nambu(self, i, opts, chi):
-        """One row of nambu_response.csv (created, with its header, by the first)."""
-        if opts["n_matsubara"] < 1:
-            return
-        if self.f_nambu is None:
-            self.f_nambu = open(os.path.join(self.out_dir, "nambu_response.csv"), "w")
-            self.f_nambu.write(nambu_csv_header(opts) + "\n")
-        self.f_nambu.write(nambu_csv_line(i, chi))
-        self.f_nambu.flush()
+    def option_row(self, i, option, values):
+        """One row of the option's CSV file (created, with its header, by the first)."""
+        f = self.csv.get(option.csv_file)
+        if f is None:
+            f = self.csv[option.csv_file] = open(os.path.join(self.out_dir, option.csv_file), "w")
+            f.write(",".join(["sweep"] + option.csv_columns()) + "\n")
+        f.write(",".join(["%d" % i] + ["%.12e" % v for v in values]) + "\n")
+        f.flush()
 
     def close(self):
-        self.f_log.close()
-        self.f_obs.close()
-        self.f_trans.close()
-        if self.f_resp is not None:
-            self.f_resp.close()
-        if self.f_oper is not None:
-            self.f_oper.close()
-        if self.f_nambu is not None:
-            self.f_nambu.close()
+        for f in (self.f_log, self.f_obs, self.f_trans, *self.csv.values()):
+            f.close()
 
 
 def thermalize(cache, p, state, out: ChainOutput, n_therm: int, Nt_therm_init: int, rng):
@@ -426,40 +453,54 @@ def thermalize(cache, p, state, out: ChainOutput, n_therm: int, Nt_therm_init: i
     return ctl.Nt, acc_therm / max(n_therm, 1)
 
 
+def record_transport(out: ChainOutput, res: SimulationResult, bin_size: int, i: int, spec, options, results,
+                     k: int) -> None:
+    """The transport measurement of sweep i into the files and res: spec's
+    row of transport.csv and its spectra into the bins, with them state k of
+    the options' results (Option.measure's, in the order of options) into the
+    bins and the options' CSV files."""
+    extra = {}
+    for o, r in zip(options, results):
+        extra.update(o.bins(r, k))
+    out.transport(i, spec, bin_size, extra or None)
+    res.transport.append((i, spec))
+    for o, r in zip(options, results):
+        if o.csv_file is not None:
+            out.option_row(i, o, o.csv_values(r, k))
+
+
 class TransportQueue:
     """Transport measurements (src/Simulation.jl:169-220) of one chain taken at
     the Δ of their sweeps and evaluated `batch` at a time: the eigensolves of
     a batch run as one batched call (dwh_measure_transport_deltas), ~3x the
     throughput of one call per sweep at L = 32.  Rows and bins come out in
     sweep order, each when its batch is measured (batch = 1: right away, as
-    the reference writes them).  spectral_maps (first / count / stride, or
-    None): every measurement also takes LDOS(i, ω) and A(k, ω) on that
-    window (measure_spectral_maps, batched the same way) into the bins.
-    current_response (direction / q / n_matsubara, or None): every
-    measurement also appends its row (sweep, dia, Λ) to current_response.csv
-    (measure_current_response, batched the same way).  operator_response
-    (ops / n_matsubara / omega / eta, or None): every measurement also
-    appends its row (sweep, χ) to operator_response.csv and puts χ''(ω) into
-    the bins as chi2 (measure_operator_response, batched the same way).
-    nambu_response (vertices / pairs / n_matsubara / omega / eta, or None):
-    every measurement also appends its row (sweep, re and im of chi) to
-    nambu_response.csv and puts the complex chi2 into the bins as nambu_chi2
-    (measure_nambu_response, batched the same way).  response_map (vertices /
-    pattern / n_matsubara / omega / eta, or None): every measurement also puts
-    the complex dmap and ρ on the pattern into the bins as response_map and
-    rho_map (measure_response_map, batched the same way)."""
+    the reference writes them).  The measurement options (OPTIONS; each
+    keyword a dict or None) are measured with every batch, each by one call
+    batched the same way."""
 
     def __init__(self, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int, chain: int = 0,
                  spectral_maps: dict | None = None, current_response: dict | None = None,
                  operator_response: dict | None = None, nambu_response: dict | None = None,
                  response_map: dict | None = None):
+        self._init(ctx, p, out, res, bin_size, batch, chain,
+                   parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
+                                 operator_response=operator_response, nambu_response=nambu_response,
+                                 response_map=response_map))
+
+    @classmethod
+    def with_options(cls, options, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int,
+                     chain: int = 0):
+        """A queue for options parsed before (parse_options), as the drivers, which parse once, make theirs."""
+        tq = cls.__new__(cls)
+        tq._init(ctx, p, out, res, bin_size, batch, chain, options)
+        return tq
+
+    def _init(self, ctx, p, out, res, bin_size, batch, chain, options):
+        """all of a queue's state, for both ways of making one"""
         self.ctx, self.p, self.out, self.res = ctx, p, out, res
         self.bin_size, self.batch, self.chain = bin_size, max(1, int(batch)), chain
-        self.window = None if spectral_maps is None else _maps_window(spectral_maps)
-        self.response = None if current_response is None else _response_opts(current_response)
-        self.operator = None if operator_response is None else _operator_opts(operator_response, p)
-        self.nambu = None if nambu_response is None else _nambu_opts(nambu_response, p)
-        self.rmap = None if response_map is None else _map_opts(response_map, p)
+        self.options = options
         self.pending = []            # (sweep, Δ snapshot)
 
     def add(self, sweep: int, Delta):
@@ -472,84 +513,15 @@ class TransportQueue:
             return
         p = self.p
         if self.batch == 1:
+            deltas = None
             specs = [self.ctx.measure_transport(p.eta, p.domega, p.omega_max, chain=self.chain)]
         else:
-            specs = self.ctx.measure_transport_deltas(np.stack([d for _, d in self.pending]), p.eta, p.domega,
-                                                      p.omega_max, chain=self.chain)
-        maps = None
-        if self.window is not None:
-            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
-            maps = self.ctx.measure_spectral_maps(p.eta, p.domega, p.omega_max, chain=self.chain, deltas=deltas,
-                                                  **self.window)
-        resp = None
-        if self.response is not None:
-            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
-            resp = self.ctx.measure_current_response(chain=self.chain, deltas=deltas, **self.response)
-            if deltas is None:
-                resp = dict(dia=[resp["dia"]], lam=[resp["lam"]])
-        oper = None
-        if self.operator is not None:
-            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
-            oper = measure_operator_option(self.ctx, self.operator, self.chain, deltas)
-        nam = None
-        if self.nambu is not None:
-            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
-            nam = measure_nambu_option(self.ctx, self.nambu, self.chain, deltas)
-        rmap = None
-        if self.rmap is not None:
-            deltas = None if self.batch == 1 else np.stack([d for _, d in self.pending])
-            rmap = measure_map_option(self.ctx, self.rmap, self.chain, deltas)
+            deltas = np.stack([d for _, d in self.pending])
+            specs = self.ctx.measure_transport_deltas(deltas, p.eta, p.domega, p.omega_max, chain=self.chain)
+        results = [o.measure(self.ctx, p, self.chain, deltas) for o in self.options]
         for k, ((i, _), r) in enumerate(zip(self.pending, specs)):
-            spec = H.SpectrumResult(**r)
-            extra = None if maps is None else {"ldos": maps["ldos"][k], "akw": maps["akw"][k]}
-            if oper is not None and self.operator["omega"] is not None:
-                extra = dict(extra or {}, chi2=oper["chi2"][k])
-            if nam is not None and self.nambu["omega"] is not None:
-                extra = dict(extra or {}, nambu_chi2=nam["chi2"][k])
-            if rmap is not None:
-                extra = dict(extra or {}, response_map=rmap["dmap"][k], rho_map=rmap["rho"][k])
-            self.out.transport(i, spec, self.bin_size, extra)
-            self.res.transport.append((i, spec))
-            if resp is not None:
-                self.out.response(i, self.response, float(resp["dia"][k]), resp["lam"][k])
-            if oper is not None:
-                self.out.operator(i, self.operator, oper["chi"][k])
-            if nam is not None:
-                self.out.nambu(i, self.nambu, nam["chi"][k])
+            record_transport(self.out, self.res, self.bin_size, i, H.SpectrumResult(**r), self.options, results, k)
         self.pending = []
-
-
-def measure_operator_option(ctx, opts: dict, chain: int, deltas) -> dict:
-    """measure_operator_response for the operator_response option: chi
-    (nstates, nops, n_matsubara) and chi2 (nstates, nops, n_w), one state at
-    the device Δ when deltas is None."""
-    r = ctx.measure_operator_response(opts["ops"], opts["spin_sign"], n_matsubara=opts["n_matsubara"],
-                                      omega=opts["omega"], eta=opts["eta"], chain=chain, deltas=deltas)
-    if deltas is None:
-        return dict(chi=r["chi"][None], chi2=r["chi2"][None])
-    return r
-
-
-def measure_nambu_option(ctx, opts: dict, chain: int, deltas) -> dict:
-    """measure_nambu_response for the nambu_response option: complex chi
-    (nstates, npairs, n_matsubara) and chi2 (nstates, npairs, n_w), one state
-    at the device Δ when deltas is None."""
-    r = ctx.measure_nambu_response(opts["vertices"], opts["pairs"], n_matsubara=opts["n_matsubara"],
-                                   omega=opts["omega"], eta=opts["eta"], chain=chain, deltas=deltas)
-    if deltas is None:
-        return dict(chi=r["chi"][None], chi2=r["chi2"][None])
-    return r
-
-
-def measure_map_option(ctx, opts: dict, chain: int, deltas) -> dict:
-    """measure_response_map for the response_map option: complex dmap
-    (nstates, nops, nz, npat) and rho (nstates, npat), one state at the device
-    Δ when deltas is None."""
-    r = ctx.measure_response_map(opts["vertices"], opts["pattern"], n_matsubara=opts["n_matsubara"],
-                                 omega=opts["omega"], eta=opts["eta"], chain=chain, deltas=deltas)
-    if deltas is None:
-        return dict(dmap=r["dmap"][None], rho=r["rho"][None])
-    return r
 
 
 def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_measure: int = 500,
@@ -569,51 +541,15 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
     transport_batch > 1 evaluates that many measurement sweeps' transport in
     one batched call (TransportQueue): same rows and bins, written up to
     transport_batch - 1 sweeps later.
-    spectral_maps = dict(first=, count=, stride=) (each optional; a window of
-    the DOS grid, FermionContext.measure_spectral_maps): every transport
-    measurement also takes LDOS(i, ω) and A(k, ω) there; each sweep_<i>.npz
-    gains their bin means ldos and akw ((count, Ly, Lx)) and
-    spectra_bins/maps_omega.npy holds the window's frequencies.  None (the
-    default): no maps, the files as without the option.
-    current_response = dict(direction=, q=, n_matsubara=) (each optional;
-    FermionContext.measure_current_response): every transport measurement
-    also appends one row (sweep, dia, then Λ(q, iΩ_l) momentum by momentum, l
-    fastest) to current_response.csv, whose header names the momenta.  None
-    (the default): no such file, everything else as without the option.
-    operator_response = dict(ops=[(kind, (mx, my)), ...], n_matsubara=,
-    omega=dict(start=, step=, count=), eta=) (each optional; kind a key of
-    vertices.KINDS; FermionContext.measure_operator_response): every transport
-    measurement also appends one row (sweep, then χ(iΩ_l) operator by
-    operator, l fastest) to operator_response.csv, whose header names kind,
-    momentum and l, and with an omega grid each sweep_<i>.npz gains the bin
-    mean chi2 ((nops, count)) with the grid in spectra_bins/chi2_omega.npy
-    (eta defaults to the run's).  None (the default): no such files,
-    everything else as without the option.
-    nambu_response = dict(vertices=[(kind, (mx, my)), ...], pairs=[(a, b), ...],
-    n_matsubara=, omega=dict(start=, step=, count=), eta=) (each optional; kind
-    a key of vertices.NAMBU_KINDS, pairs indices into vertices, default every
-    (k, k); FermionContext.measure_nambu_response): every transport
-    measurement also appends one row (sweep, then re and im of chi pair by
-    pair, l fastest) to nambu_response.csv, whose header names each pair's
-    vertices and l, and with an omega grid each sweep_<i>.npz gains the complex
-    bin mean nambu_chi2 ((npairs, count)) with the grid in
-    spectra_bins/nambu_chi2_omega.npy.  None (the default): no such files,
-    everything else as without the option.
-    response_map = dict(vertices=[(kind, (mx, my)), ...], pattern=dict(ranges=,
-    blocks=) or an (npat, 2) array, n_matsubara=, omega=[ω, ...], eta=) (each
-    optional; kind a key of vertices.NAMBU_KINDS, default the q = 0 x current
-    on the whole vertices.bond_pattern; FermionContext.measure_response_map):
-    every transport measurement also takes the linear-response density matrix
-    of each source vertex and ρ on the pattern; each sweep_<i>.npz gains their
-    complex bin means response_map ((nops, nz, npat)) and rho_map ((npat,)),
-    and spectra_bins/response_map_pattern.npy holds the pattern.  None (the
-    default): no such files, everything else as without the option."""
+    spectral_maps, current_response, operator_response, nambu_response,
+    response_map: the measurement options (OPTIONS), each a dict that its
+    description documents (SpectralMaps, CurrentResponse, OperatorResponse,
+    NambuResponse, ResponseMap) or None (the default): the files as without
+    the option.  All are checked before any file is opened."""
     rng = rng if rng is not None else np.random.default_rng()
-    if current_response is not None:
-        _response_opts(current_response)
-    oper_opts = None if operator_response is None else _operator_opts(operator_response, p)
-    nambu_opts = None if nambu_response is None else _nambu_opts(nambu_response, p)
-    map_opts = None if response_map is None else _map_opts(response_map, p)
+    options = parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
+                            operator_response=operator_response, nambu_response=nambu_response,
+                            response_map=response_map)
     out = ChainOutput(out_dir, verbose)
     try:
         out.header(p, n_therm, n_measure, measure_transport_freq, bin_size)
@@ -625,15 +561,7 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         H.update_H_BdG(cache, p, state)
         H.diagonalize_H_BdG(cache, p)
         if measure_transport_freq > 0:
-            write_spectra_header(out.spec_dir, p)
-            if spectral_maps is not None:
-                write_maps_header(out.spec_dir, p, spectral_maps)
-            if oper_opts is not None:
-                write_chi2_header(out.spec_dir, oper_opts)
-            if nambu_opts is not None:
-                write_nambu_header(out.spec_dir, nambu_opts)
-            if map_opts is not None:
-                write_map_header(out.spec_dir, map_opts)
+            write_headers(out.spec_dir, p, options)
         Nt_fin, acc_th = thermalize(cache, p, state, out, n_therm, Nt_therm_init, rng)
 
         dt_meas = H.calc_optimal_dt(p.beta, p.J, p.mass, Nt_measure)
@@ -642,9 +570,7 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         t1 = time.time()
         acc_total = 0
         res = SimulationResult(Nt_fin, acc_th, 0.0)
-        tq = TransportQueue(cache.require(), p, out, res, bin_size, transport_batch, spectral_maps=spectral_maps,
-                            current_response=current_response, operator_response=operator_response,
-                            nambu_response=nambu_opts, response_map=map_opts)
+        tq = TransportQueue.with_options(options, cache.require(), p, out, res, bin_size, transport_batch)
         for i in range(1, n_measure + 1):
             acc, dH = H.hmc_sweep(cache, p, state, Nt=Nt_measure, dt=dt_meas, rng=rng)
             acc_total += int(acc)
@@ -688,11 +614,9 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
     differ).  spectral_maps, current_response, operator_response,
     nambu_response, response_map: as run_simulation's, for every chain."""
     K = len(out_dirs)
-    window = None if spectral_maps is None else _maps_window(spectral_maps)
-    response = None if current_response is None else _response_opts(current_response)
-    oper_opts = None if operator_response is None else _operator_opts(operator_response, p)
-    nambu_opts = None if nambu_response is None else _nambu_opts(nambu_response, p)
-    map_opts = None if response_map is None else _map_opts(response_map, p)
+    options = parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
+                            operator_response=operator_response, nambu_response=nambu_response,
+                            response_map=response_map)
     if len(rngs) != K or K < 1:
         raise ValueError("one rng per output directory")
     outs = [ChainOutput(d, verbose) for d in out_dirs]
@@ -706,15 +630,7 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
             H.update_H_BdG(cache, p, st)
             H.diagonalize_H_BdG(cache, p)
             if measure_transport_freq > 0:
-                write_spectra_header(outs[k].spec_dir, p)
-                if spectral_maps is not None:
-                    write_maps_header(outs[k].spec_dir, p, spectral_maps)
-                if oper_opts is not None:
-                    write_chi2_header(outs[k].spec_dir, oper_opts)
-                if nambu_opts is not None:
-                    write_nambu_header(outs[k].spec_dir, nambu_opts)
-                if map_opts is not None:
-                    write_map_header(outs[k].spec_dir, map_opts)
+                write_headers(outs[k].spec_dir, p, options)
             Nt_fin, acc_th = thermalize(cache, p, st, outs[k], n_therm, Nt_therm_init, rngs[k])
             cache.ctx.close()
             states.append(st)
@@ -732,10 +648,7 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                 o.tee(f"Settings: Nt={Nt_measure}, dt={round(dt_meas, 5)}")
             t1 = time.time()
             acc_total = np.zeros(K, dtype=np.int64)
-            tqs = [TransportQueue(ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k,
-                                  spectral_maps=spectral_maps, current_response=current_response,
-                                  operator_response=operator_response, nambu_response=nambu_opts,
-                                  response_map=map_opts)
+            tqs = [TransportQueue.with_options(options, ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k)
                    for k in range(K)] if transport_batch > 1 else None
             for i in range(1, n_measure + 1):
                 noise = np.stack([H.standard_complex_normal(r, (p.N, 2)) for r in rngs])
@@ -757,29 +670,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                     outs[k].observables(i, acc[k], float(dH[k]), obs)
                     results[k].records.append((i, bool(acc[k]), float(dH[k]), obs))
                     if specs is not None:
-                        spec = H.SpectrumResult(**specs[k])
-                        maps = None
-                        if window is not None:
-                            m = ctx.measure_spectral_maps(p.eta, p.domega, p.omega_max, chain=k, **window)
-                            maps = {"ldos": m["ldos"][0], "akw": m["akw"][0]}
-                        oper = None if oper_opts is None else measure_operator_option(ctx, oper_opts, k, None)
-                        if oper is not None and oper_opts["omega"] is not None:
-                            maps = dict(maps or {}, chi2=oper["chi2"][0])
-                        nam = None if nambu_opts is None else measure_nambu_option(ctx, nambu_opts, k, None)
-                        if nam is not None and nambu_opts["omega"] is not None:
-                            maps = dict(maps or {}, nambu_chi2=nam["chi2"][0])
-                        if map_opts is not None:
-                            rm = measure_map_option(ctx, map_opts, k, None)
-                            maps = dict(maps or {}, response_map=rm["dmap"][0], rho_map=rm["rho"][0])
-                        outs[k].transport(i, spec, bin_size, maps)
-                        results[k].transport.append((i, spec))
-                        if response is not None:
-                            r = ctx.measure_current_response(chain=k, **response)
-                            outs[k].response(i, response, r["dia"], r["lam"])
-                        if oper is not None:
-                            outs[k].operator(i, oper_opts, oper["chi"][0])
-                        if nam is not None:
-                            outs[k].nambu(i, nambu_opts, nam["chi"][0])
+                        record_transport(outs[k], results[k], bin_size, i, H.SpectrumResult(**specs[k]), options,
+                                         [o.measure(ctx, p, k, None) for o in options], 0)
                     if i % 10 == 0:
                         outs[k].tee("Meas %d/%d. Acc=%.2f. E=%.4f" % (i, n_measure, acc_total[k] / i,
                                                                      obs.total_energy))

@@ -28,13 +28,13 @@ Every column of J_nm is computed on the device (no particle-hole half sum), so
 nothing here depends on DWHMC_EIG_HALF.
 """
 import ctypes as C
-import importlib
 import os
 
 import numpy as np
 import pytest
 
-from oracle_context import OracleContext
+from oracle_measurements import CurrentRef as _Ref, OracleResponse as _OracleResponse, jq as _jq, \
+    simulate as _simulate
 
 T, TP, MU = 1.0, -0.35, -1.08
 TOL = 1e-9
@@ -55,62 +55,6 @@ def _clean(O, L, mu, beta=8.0):
     p = O.ModelParameters(L, L, T, TP, mu, 0.0, 0.0, beta, 0.8, 1.0)
     D = np.stack([np.full(p.N, 0.2), np.full(p.N, -0.2)], 1).astype(np.complex128)
     return p, np.zeros(p.N), D
-
-
-def _bonds(p, a):
-    """(neighbour j_b (0-based), hopping t_b, bond vector δ_b) of direction a."""
-    nn, nnn = p.nn_table - 1, p.nnn_table - 1
-    if a == "x":
-        return [(nn[:, 0], p.t, (1, 0)), (nnn[:, 0], p.tp, (1, 1)), (nnn[:, 3], p.tp, (1, -1))]
-    return [(nn[:, 1], p.t, (0, 1)), (nnn[:, 0], p.tp, (1, 1)), (nnn[:, 1], p.tp, (-1, 1))]
-
-
-def _jq(p, a, mx, my):
-    """Particle block of J_a(q): the triplet sum, duplicates added."""
-    N = p.N
-    qx, qy = 2 * np.pi * mx / p.Lx, 2 * np.pi * my / p.Ly
-    J = np.zeros((N, N), dtype=np.complex128)
-    for i in range(N):
-        x, y = i % p.Lx, i // p.Lx
-        for j, tb, (dx, dy) in _bonds(p, a):
-            val = 1j * tb * np.exp(-1j * (qx * (x + dx / 2) + qy * (y + dy / 2)))
-            J[i, j[i]] += val
-            J[j[i], i] -= val
-    return J
-
-
-class _Ref:
-    """numpy response of one (p, disorder, Δ): the eigenpairs once."""
-
-    def __init__(self, O, p, dis, D):
-        cache, _, _ = O.evaluate(p, dis, D)
-        self.p, self.E, self.U, self.f = p, cache.E_n.copy(), cache.U.copy(), cache.fermi_factors.copy()
-
-    def dia(self, a):
-        p, N, E = self.p, self.p.N, self.E
-        u, v = self.U[:N], self.U[N:]
-        i = np.arange(N)
-        w = sum(tb * 2.0 * np.real(v[i] * np.conj(v[j]) - np.conj(u[i]) * u[j]).sum(axis=0) for j, tb, _ in _bonds(p, a))
-        pos = E > 0
-        return float(np.sum(w[pos] * np.tanh(0.5 * p.beta * E[pos]))) / N
-
-    def lam(self, a, qs, nl):
-        p, N, E, U, f = self.p, self.p.N, self.E, self.U, self.f
-        u, v = U[:N], U[N:]
-        dE = E[None, :] - E[:, None]                     # [n, m]: E_m - E_n
-        df = f[:, None] - f[None, :]
-        deg = np.abs(dE) < 1e-8
-        out = np.empty((len(qs), nl))
-        for k, (mx, my) in enumerate(qs):
-            J = _jq(p, a, mx, my)
-            J2 = np.abs(U.conj().T @ np.vstack([J @ u, J @ v])) ** 2
-            for l in range(nl):
-                if l == 0:
-                    r = np.where(deg, (p.beta * f * (1.0 - f))[:, None], df / np.where(deg, 1.0, dE))
-                else:
-                    r = df * dE / (dE * dE + (2 * np.pi * l / p.beta) ** 2)
-                out[k, l] = float(np.sum(r * J2)) / N
-        return out
 
 
 def _close(a, b, what=""):
@@ -213,35 +157,6 @@ def test_debug_current_vertex(dwhmc, oracle, Lx, Ly, a):
             _close(blk.imag, J.imag, (a, mx, my, "im"))
         assert not got[k, :N, N:].any() and not got[k, N:, :N].any()
     assert np.abs(got).max() > 0.1                          # (Lx = 2, x, q = 0 alone cancels to zero)
-
-
-class _OracleResponse(OracleContext):
-    """OracleContext + measure_current_response by the numpy restatement."""
-
-    def measure_current_response(self, direction="x", q=((0, 1),), n_matsubara=1, chain=0, deltas=None):
-        from oracle import dwhmc_oracle as O
-        qs = [tuple(k) for k in q]
-        fields = [self.Delta[chain]] if deltas is None else list(np.asarray(deltas))
-        refs = [_Ref(O, self.p, self.dis[chain], D) for D in fields]
-        dia = np.array([r.dia(direction) for r in refs])
-        lam = np.stack([r.lam(direction, qs, n_matsubara) for r in refs])
-        return dict(dia=float(dia[0]), lam=lam[0]) if deltas is None else dict(dia=dia, lam=lam)
-
-
-def _simulate(dwhmc, out_dir, ctx_cls, chains=0, **kw):
-    sim = importlib.import_module(dwhmc.__name__ + ".simulation")
-    hmc_mod = importlib.import_module(dwhmc.__name__ + ".hmc")
-    p = dwhmc.ModelParameters(4, 4, 1.0, -0.35, -1.08, 1.0, 0.25, 8.0, 0.8, 1.0)
-    saved = hmc_mod.FermionContext
-    if ctx_cls is not None:
-        hmc_mod.FermionContext = ctx_cls
-    try:
-        if chains:
-            return sim.run_simulation_chains(p, [str(out_dir / f"c{k}") for k in range(chains)],
-                                             [np.random.default_rng(21 + k) for k in range(chains)], **kw)
-        return sim.run_simulation(p, str(out_dir), rng=np.random.default_rng(21), verbose=False, **kw)
-    finally:
-        hmc_mod.FermionContext = saved
 
 
 SIM_KW = dict(n_therm=3, n_measure=4, Nt_therm_init=2, Nt_measure=12, bin_size=2)

@@ -23,8 +23,8 @@ import pytest
 
 import measure_cases as MC
 import measure_reference as R
-from test_current_response import QLIST, _Ref as RefCurrent, _case
-from test_operator_response import _Ref as RefOperator
+from oracle_measurements import CurrentRef as RefCurrent, OperatorRef as RefOperator
+from test_current_response import QLIST, _case
 
 LD, F8 = np.longdouble, np.float64
 EPS_LD = float(np.finfo(LD).eps)

@@ -34,8 +34,9 @@ import pytest
 
 import measure_reference as R
 from nambu_reference import LD, NRef, OracleNambu, grid as _grid
-from test_current_response import SIM_KW, T, TP, MU, _case, _ctx, _simulate
-from test_operator_response import _Ref as _RefOperator, _bands
+from oracle_measurements import OperatorRef as _RefOperator, simulate as _simulate
+from test_current_response import SIM_KW, T, TP, MU, _case, _ctx
+from test_operator_response import _bands
 
 TOL = 1e-9
 NL = 3

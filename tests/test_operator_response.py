@@ -33,67 +33,14 @@ import os
 import numpy as np
 import pytest
 
-from oracle_context import OracleContext
-from test_current_response import SIM_KW, T, TP, MU, _Ref as _RefCurrent, _case, _clean, _ctx, _jq, _simulate
+from oracle_measurements import CurrentRef as _RefCurrent, OperatorRef as _Ref, OracleOperator as _OracleOperator, \
+    grid as _grid, jq as _jq, nambu as _nambu, simulate as _simulate
+from test_current_response import SIM_KW, T, TP, MU, _case, _clean, _ctx
 
 TOL = 1e-9
 NL = 3
 ETA = 0.05
 OMEGA = (-0.6, 0.3, 5)          # -0.6, -0.3, 0, 0.3, 0.6
-
-
-def _grid(omega):
-    return omega[0] + omega[1] * np.arange(omega[2])
-
-
-def _nambu(V, s):
-    N = V.shape[0]
-    Z = np.zeros((N, N), dtype=np.complex128)
-    return np.block([[V, Z], [Z, -s * V.T]])
-
-
-class _Ref:
-    """numpy response of one (p, disorder, Δ): the eigenpairs once."""
-
-    def __init__(self, O, p, dis, D):
-        cache, _, _ = O.evaluate(p, dis, D)
-        self.p, self.E, self.U, self.f = p, cache.E_n.copy(), cache.U.copy(), cache.fermi_factors.copy()
-
-    def v2(self, V, s):
-        return np.abs(self.U.conj().T @ _nambu(np.asarray(V, dtype=np.complex128), s) @ self.U) ** 2
-
-    def chi(self, V, s, nl):
-        p, E, f = self.p, self.E, self.f
-        dE = E[None, :] - E[:, None]                     # [n, m]: E_m - E_n
-        df = f[:, None] - f[None, :]
-        deg = np.abs(dE) < 1e-8
-        V2 = self.v2(V, s)
-        out = np.empty(nl)
-        for l in range(nl):
-            if l == 0:
-                r = np.where(deg, (p.beta * f * (1.0 - f))[:, None], df / np.where(deg, 1.0, dE))
-            else:
-                r = df * dE / (dE * dE + (2 * np.pi * l / p.beta) ** 2)
-            out[l] = float(np.sum(r * V2)) / p.N
-        return out
-
-    def skipped_share(self):
-        df = self.f[:, None] - self.f[None, :]
-        return float(np.mean(np.abs(df) < 1e-12))
-
-    def chi2(self, V, s, w, eta, reverse=False):
-        E, f = self.E, self.f
-        dE = (E[None, :] - E[:, None]).ravel()
-        df = (f[:, None] - f[None, :]).ravel()
-        keep = np.abs(df) >= 1e-12
-        c, dE = (df * self.v2(V, s).ravel())[keep], dE[keep]
-        if reverse:
-            c, dE = c[::-1], dE[::-1]
-        out = np.empty(len(w))
-        for j, wj in enumerate(np.asarray(w, dtype=np.float64)):
-            x = wj - dE
-            out[j] = np.pi / self.p.N * float(np.sum(c * ((1.0 / np.pi) * eta / (x * x + eta * eta))))
-        return out
 
 
 def _close(a, b, what=""):
@@ -392,23 +339,6 @@ def test_null_context_is_refused(dwhmc):
     assert b"NULL" in lib.dwh_last_error(None)
     assert dwhmc.FermionContext.TIMERS.index("response") == 13
     assert dwhmc.FermionContext.TIMERS.index("operator") == 14
-
-
-class _OracleOperator(OracleContext):
-    """OracleContext + measure_operator_response by the numpy restatement."""
-
-    def measure_operator_response(self, ops, spin_sign=None, n_matsubara=1, omega=None, eta=None, chain=0,
-                                  deltas=None):
-        from oracle import dwhmc_oracle as O
-        fields = [self.Delta[chain]] if deltas is None else list(np.asarray(deltas))
-        refs = [_Ref(O, self.p, self.dis[chain], D) for D in fields]
-        w = np.zeros(0) if omega is None else _grid(omega)
-        dense = [(v.dense(self.N), s) for v, s in zip(ops, spin_sign)]
-        chi = np.stack([np.stack([r.chi(V, s, n_matsubara) for V, s in dense]) for r in refs])
-        chi2 = np.stack([np.stack([r.chi2(V, s, w, eta) for V, s in dense]) for r in refs])
-        if deltas is None:
-            return dict(chi=chi[0], chi2=chi2[0], omega=w)
-        return dict(chi=chi, chi2=chi2, omega=w)
 
 
 SIM_OPS = [("density", (1, 0)), ("spin", (0, 0)), ("raman_b1g", (0, 0))]

@@ -37,7 +37,8 @@ import pytest
 import measure_reference as R
 from nambu_reference import LD
 from response_map_reference import MapRef, OracleMap
-from test_current_response import SIM_KW, _Ref as _RefCurrent, _case, _ctx, _simulate
+from oracle_measurements import CurrentRef as _RefCurrent, simulate as _simulate
+from test_current_response import SIM_KW, _case, _ctx
 from test_nambu_response import ETA, TOL, _close, _close_max, _free, _injected_spectrum, _random_w, _vset
 
 NL = 3

@@ -29,7 +29,7 @@ import types
 import numpy as np
 import pytest
 
-from oracle_context import OracleContext
+from oracle_measurements import MapsRef as _Ref, OracleMaps as _OracleMaps, simulate as _simulate
 
 T, TP, MU = 1.0, -0.35, -1.08
 ETA, DW, WMAX = 0.01, 0.002, 4.0      # the default grid: 4001 DOS points
@@ -44,25 +44,6 @@ def _case(O, Lx, Ly, beta, seed, W=1.0, nimp=0.1, amp=0.25, mu=MU):
     N = p.N
     D = st.Delta + amp * np.stack([np.ones(N), -np.ones(N)], 1) * np.exp(0.3j * rng.standard_normal((N, 1)))
     return p, st.disorder_pot, D
-
-
-class _Ref:
-    """numpy maps of one (p, disorder, Δ): the eigenpairs once, any window after."""
-
-    def __init__(self, O, p, dis, D):
-        cache, _, _ = O.evaluate(p, dis, D)
-        self.O, self.p = O, p
-        N = p.N
-        self.E = cache.E_n.copy()
-        u = cache.U[:N]                                                   # (N, 2N)
-        self.w_site = np.abs(u) ** 2
-        uk = np.fft.fft2(u.T.reshape(2 * N, p.Ly, p.Lx), axes=(1, 2))     # [n, ky, kx]
-        self.w_k = (np.abs(uk.reshape(2 * N, N)) ** 2 / N).T              # (N, 2N), k = kx + Lx ky
-
-    def maps(self, omega, eta=ETA):
-        lam = self.O.lorentzian(omega[None, :] - self.E[:, None], eta)    # (2N, count)
-        shape = (len(omega), self.p.Ly, self.p.Lx)
-        return (self.w_site @ lam).T.reshape(shape), (self.w_k @ lam).T.reshape(shape)
 
 
 def _close(a, b, what=""):
@@ -148,36 +129,6 @@ def test_bins_accumulate_maps(dwhmc, tmp_path):
         b.add(s)
     b.flush(str(tmp_path), 12)
     assert sorted(np.load(tmp_path / "sweep_12.npz").files) == ["A_k0", "count", "dos", "dos_AN", "opt_cond"]
-
-
-class _OracleMaps(OracleContext):
-    """OracleContext + measure_spectral_maps by the numpy restatement."""
-
-    def measure_spectral_maps(self, eta, domega, omega_max, first=0, count=None, stride=1, chain=0, deltas=None,
-                              ldos=True, akw=True):
-        import dataclasses
-        from oracle import dwhmc_oracle as O
-        omega = O.julia_range(-omega_max, domega, omega_max)[first::stride][:count]
-        fields = [self.Delta[chain]] if deltas is None else list(np.asarray(deltas))
-        p = dataclasses.replace(self.p, eta=eta, domega=domega, omega_max=omega_max)
-        both = [_Ref(O, p, self.dis[chain], D).maps(omega, eta) for D in fields]
-        return dict(omega=omega, ldos=np.stack([m[0] for m in both]), akw=np.stack([m[1] for m in both]))
-
-
-def _simulate(dwhmc, out_dir, ctx_cls, chains=0, **kw):
-    sim = importlib.import_module(dwhmc.__name__ + ".simulation")
-    hmc_mod = importlib.import_module(dwhmc.__name__ + ".hmc")
-    p = dwhmc.ModelParameters(4, 4, 1.0, -0.35, -1.08, 1.0, 0.25, 8.0, 0.8, 1.0)
-    saved = hmc_mod.FermionContext
-    if ctx_cls is not None:
-        hmc_mod.FermionContext = ctx_cls
-    try:
-        if chains:
-            return sim.run_simulation_chains(p, [str(out_dir / f"c{k}") for k in range(chains)],
-                                             [np.random.default_rng(21 + k) for k in range(chains)], **kw)
-        return sim.run_simulation(p, str(out_dir), rng=np.random.default_rng(21), verbose=False, **kw)
-    finally:
-        hmc_mod.FermionContext = saved
 
 
 SIM_KW = dict(n_therm=4, n_measure=4, Nt_therm_init=2, Nt_measure=3, bin_size=2)
