@@ -105,6 +105,8 @@ SIGNATURES = {
                                            _P, _P, _P]),
     "dwh_debug_response_map_plan": (C.c_int, [_I64, _I64, _P, _P, _P, _P]),
     "dwh_bench_response_map_stages": (C.c_int, [_P, _I64, _I64, _DP, _DP]),
+    "dwh_measure_correlations": (C.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P]),
+    "dwh_debug_correlation_dense": (C.c_int, [_I64, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _P]),
     "dwh_debug_dense_H": (C.c_int, [_P, _I64, _P]),
     "dwh_debug_qeig": (C.c_int, [_P, _I64, _P, _P]),
     "dwh_debug_set_eigensystem": (C.c_int, [_P, _I64, _P, _P, _I32]),

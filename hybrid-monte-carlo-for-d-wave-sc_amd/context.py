@@ -420,6 +420,56 @@ class FermionContext:
             nl, 0.0 if eta is None else float(eta), nw, ptr(w) if nw > 0 else None, ptr(r), ptr(dmap)))
         return dict(_per_state(deltas, dmap=dmap, rho=r), pattern=pat, omega=w)
 
+    def measure_correlations(self, families, pairs=None, ref_sites=None, mean: bool = True, chain: int = 0,
+                             deltas=None, corr: bool = True) -> dict:
+        """Equal-time correlations of local operators (dwh_measure_correlations):
+        C_AB(r) = (1/N) Σ_j G_AB(j ⊕ r, j), G_AB(i, j) = <O_A(i) O_B(j)†> -
+        <O_A(i)><O_B(j)†> by Wick's theorem from the full ρ = U f U^H.
+        families: a list of vertices.LocalFamily (vertices.local_family builds
+        the named ones), or the term table (tptr, trow, tcol, tval) itself.
+        pairs: list of (a, b) indices into the families (None: every (k, k)).
+        ref_sites: sites around which the untranslated G(ref ⊕ r, ref) is
+        returned too (None: no local output).  mean=False / corr=False skip
+        those outputs (corr= is this binding's own switch for the ABI's
+        nullable corr).  At the device Δ of `chain` or at the pairing fields
+        `deltas` ((nstates, N, 2)).  Returns corr ((nstates,) npairs, Ly, Lx)
+        at [ry, rx] or None, local ((nstates,) npairs, nref, Ly, Lx) or None,
+        mean ((nstates,) nfam, Ly, Lx) at [y, x] or None, and pairs (npairs, 2).
+        The disconnected part is vertices.disconnected(p, mean[a], mean[b])."""
+        from . import vertices as vx
+        N = self.N
+        Lx, Ly = self.info_lattice
+        if isinstance(families, tuple) and len(families) == 4 and not isinstance(families, vx.LocalFamily) \
+                and not isinstance(families[0], vx.LocalFamily):          # (else: four families in a tuple)
+            tptr = np.ascontiguousarray(families[0], dtype=np.int64).ravel()
+            trow = np.ascontiguousarray(families[1], dtype=np.int64).ravel()
+            tcol = np.ascontiguousarray(families[2], dtype=np.int64).ravel()
+            tval = np.ascontiguousarray(families[3], dtype=np.complex128).ravel()
+            if len(tptr) < 1 or (len(tptr) - 1) % N or not (len(trow) == len(tcol) == len(tval)) \
+                    or tptr[-1] != len(tval):
+                raise ValueError("families: a term table needs tptr of nfam N + 1 entries ending at the term count")
+        else:
+            if isinstance(families, vx.LocalFamily):
+                families = [families]
+            tptr, trow, tcol, tval = vx.local_terms(families, N)
+        nfam = (len(tptr) - 1) // N
+        if pairs is None:
+            pr = np.stack([np.arange(nfam, dtype=np.int64)] * 2, axis=1)
+        else:
+            pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        pr = np.ascontiguousarray(pr)
+        npairs = pr.shape[0]
+        ref = None if ref_sites is None else np.ascontiguousarray(np.asarray(ref_sites, dtype=np.int64).ravel())
+        nref = 0 if ref is None else len(ref)
+        ns, D = self._states(deltas)
+        out_m = np.empty((ns, nfam, Ly, Lx), dtype=np.complex128) if mean else None
+        out_c = np.empty((ns, npairs, Ly, Lx), dtype=np.complex128) if corr else None
+        out_l = np.empty((ns, npairs, nref, Ly, Lx), dtype=np.complex128) if ref is not None else None
+        self._c(self._lib.dwh_measure_correlations(
+            self._h, int(chain), ns, ptr(D), nfam, ptr(tptr), ptr(trow), ptr(tcol), ptr(tval), npairs, ptr(pr),
+            nref, ptr(ref), ptr(out_m), ptr(out_c), ptr(out_l)))
+        return dict(_per_state(deltas, corr=out_c, local=out_l, mean=out_m), pairs=pr)
+
     # -- assembly read-back (parity tests) --------------------------------
     def debug_dense_H(self, chain: int = 0) -> np.ndarray:
         """H_BdG(Δ) (2N, 2N) as the eigen/transport path assembles it (dwh_debug_dense_H)."""
@@ -474,7 +524,7 @@ class FermionContext:
     # -- timing ----------------------------------------------------------
     TIMERS =("gj_update", "gj_pivot", "assemble", "contract", "step", "gj_edge", "cr_gemm", "cr_inv",
               "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral", "response", "operator",
-              "nambu", "map")
+              "nambu", "map", "corr_rho", "corr_contract", "corr_reduce")
 
     def timing_enable(self, on=True):
         """on: True (all timers), False, or an iterable of timer names."""

@@ -23,7 +23,8 @@ namespace dwh {
 
 enum TimerName {
   T_GJ_UPDATE = 0, T_GJ_PIVOT, T_ASSEMBLE, T_CONTRACT, T_STEP, T_GJ_EDGE, T_CR_GEMM, T_CR_INV, T_CR_INVSIDE,
-  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_OPERATOR, T_NAMBU, T_MAP, T_COUNT
+  T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_OPERATOR, T_NAMBU, T_MAP,
+  T_CORR_RHO, T_CORR_CONTRACT, T_CORR_REDUCE, T_COUNT
 };
 inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assemble", "contract",
                                                  "step",      "gj_edge",  "cr_gemm",  "cr_inv",
@@ -34,7 +35,10 @@ inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assem
                                                  "response",    // Λ(q, iΩ) after its eigensolve (work: flops)
                                                  "operator",    // χ(iΩ), χ''(ω) of sparse vertices after their eigensolve (work: flops)
                                                  "nambu",       // cross response of Nambu vertices after its eigensolve (work: flops)
-                                                 "map"};        // response maps after their eigensolve (work: flops)
+                                                 "map",         // response maps after their eigensolve (work: flops)
+                                                 "corr_rho",       // correlations: ρ = U f U^H (work: flops)
+                                                 "corr_contract",  // ... the Wick contractions (work: bytes issued)
+                                                 "corr_reduce"};   // ... chunk sums and the mean gather (work: bytes)
 
 enum Algo { ALGO_DENSE = 0, ALGO_CR = 1, ALGO_EIG = 2 };
 
@@ -185,6 +189,14 @@ struct dwh_ctx {
   // what the last call with a dmap output left there, for dwh_bench_response_map_stages:
   // slices, entries, frequencies per chunk, and where in d_rs_ws its last X lies
   int64_t map_last_nslices = 0, map_last_npat = 0, map_last_chunk = 0, map_last_x = 0;
+  // equal-time correlations: d_cr_idx the call's term table, pair list and
+  // reference sites (tptr, trow, tcol, pairs, ref, one after the other),
+  // d_cr_val the term values, d_cr_part the translation average's partials
+  // (pairs x chunks x N), d_cr_out one state's mean, corr and local.  ρ itself
+  // takes the slot's Jmn (S = diag(f) U^H its JU).
+  int64_t cr_nidx = 0, cr_nval = 0, cr_npart = 0, cr_nout = 0;
+  int* d_cr_idx = nullptr;
+  double2 *d_cr_val = nullptr, *d_cr_part = nullptr, *d_cr_out = nullptr;
   // own eigensolver (dwhmc_eig.hip) workspace for eig_slots matrices: hemv
   // partials, v ping-pong, w, tridiagonal (d, e), tau, compact-WY T blocks and
   // the back-transform's two nb x n products; the n x n work lives in the

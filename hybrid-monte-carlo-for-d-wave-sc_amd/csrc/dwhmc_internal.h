@@ -457,6 +457,28 @@ void launch_map_fscale(const double2* UH, int N, const double* f, double2* S, hi
 void launch_map_sddmm(const double2* UH, const double2* S, int64_t sS, int N, const int* slices, int nslices,
                       const int* arow, const int* dst, double2* out, int64_t sOut, int nmat, hipStream_t s);
 
+// Equal-time correlations of local families (dwhmc_corr.hip), one state at a
+// time, from the full ρ = U f U^H (n2 x n2 column-major).  The terms of family
+// k at site i are tptr[k N + i] .. tptr[k N + i + 1] - 1 of (trow, tcol, tval);
+// pairs: 2 ints (a_p, b_p) per pair; all on the device.
+constexpr int kCorrTile = 256;      // displacements r per workgroup, a lane each
+// sites j per workgroup of the translation average: a compile-time constant,
+// because the association of the sum over j depends on it
+constexpr int kCorrChunk = 16;
+constexpr int kCorrMaxTerms = 64;   // most terms at one (family, site)
+constexpr int kCorrMaxN2 = 8192;
+inline int corr_chunks(int N) { return cdiv(N, kCorrChunk); }
+// jlist == NULL: part[(p corr_chunks(N) + c) N + r] = Σ_{j in chunk c} G_p(j ⊕ r, j), nj = N;
+// else part[(p nj + q) N + r] = G_p(jlist[q] ⊕ r, jlist[q]), q < nj
+void launch_corr(const double2* rho, int N, int Lx, const int* tptr, const int* trow, const int* tcol,
+                 const double2* tval, const int* pairs, int npairs, const int* jlist, int nj, double2* part,
+                 hipStream_t s);
+// out[p N + r] = (1/N) Σ_c part[(p corr_chunks(N) + c) N + r], c ascending
+void launch_corr_sum(const double2* part, int N, int npairs, double2* out, hipStream_t s);
+// out[k N + i] = Σ_t a_{i,t} ρ[c(i,t), r(i,t)] over the terms of family k at site i
+void launch_corr_mean(const double2* rho, int N, const int* tptr, const int* trow, const int* tcol,
+                      const double2* tval, int nfam, double2* out, hipStream_t s);
+
 // Eigendecomposition leapfrog step (algo eig; U, JU, rho: nc chains of n2 x n2
 // column-major, E: nc x n2): JU = U diag(logistic(-β E)); after rho = JU U^H,
 // P at the bonds, Tr ρ_hh and E_f per chain

@@ -45,7 +45,8 @@ void response_release(dwh_ctx* ctx) {
   for (void* q : {(void*)ctx->d_rs_ws, (void*)ctx->d_rs_val, (void*)ctx->d_rs_part, (void*)ctx->d_rs_out,
                   (void*)ctx->d_rs_col, (void*)ctx->d_rs_idx, (void*)ctx->d_rs_nbr, (void*)ctx->d_op_part,
                   (void*)ctx->d_nb_x, (void*)ctx->d_nb_part, (void*)ctx->d_nb_pairs, (void*)ctx->d_map_ws,
-                  (void*)ctx->d_map_out, (void*)ctx->d_map_omega, (void*)ctx->d_map_idx, (void*)ctx->d_map_slice})
+                  (void*)ctx->d_map_out, (void*)ctx->d_map_omega, (void*)ctx->d_map_idx, (void*)ctx->d_map_slice,
+                  (void*)ctx->d_cr_idx, (void*)ctx->d_cr_val, (void*)ctx->d_cr_part, (void*)ctx->d_cr_out})
     drop_alloc(ctx, q);
   ctx->d_rs_ws = ctx->d_rs_val = ctx->d_nb_x = nullptr;
   ctx->d_rs_part = ctx->d_rs_out = ctx->d_op_part = ctx->d_nb_part = nullptr;
@@ -57,6 +58,9 @@ void response_release(dwh_ctx* ctx) {
   ctx->d_map_idx = ctx->d_map_slice = nullptr;
   ctx->map_nws = ctx->map_nout = ctx->map_nomega = ctx->map_nidx = ctx->map_nslice = 0;
   ctx->map_last_nslices = ctx->map_last_npat = ctx->map_last_chunk = ctx->map_last_x = 0;
+  ctx->d_cr_idx = nullptr;
+  ctx->d_cr_val = ctx->d_cr_part = ctx->d_cr_out = nullptr;
+  ctx->cr_nidx = ctx->cr_nval = ctx->cr_npart = ctx->cr_nout = 0;
 }
 
 }  // namespace
@@ -244,13 +248,13 @@ int check_state_args(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c12
 
 // fn(src, m, s0) on the states of a call: the chain's own Δ on the device
 // (Delta == NULL, one state), else the nstates snapshots staged and taken in
-// groups of tr_group, m states from state s0 per call
+// groups of tr_group (cap > 0: of at most cap), m states from state s0 per call
 template <class F>
-int for_each_state_group(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta, F&& fn) {
+int for_each_state_group(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta, F&& fn, int cap = 0) {
   if (!Delta) return fn(chains_src(ctx, chain), 1, (int64_t)0);
   if (int rc = stage_deltas(ctx, nstates, Delta)) return rc;
   const int64_t n2 = 2 * (int64_t)ctx->d.N;
-  const int group = tr_group(ctx, nstates);
+  const int group = cap > 0 ? std::min(cap, tr_group(ctx, nstates)) : tr_group(ctx, nstates);
   for (int64_t s0 = 0; s0 < nstates; s0 += group) {
     const int m = (int)std::min<int64_t>(group, nstates - s0);
     if (int rc = fn(TrSrc{ctx->d_tr_stage + s0 * n2, n2, chain, 0}, m, s0)) return rc;
@@ -908,6 +912,162 @@ int map_run(dwh_ctx* ctx, const TrSrc& src, int m, const Vertex& v, int64_t nops
   return lrc;
 }
 
+// ---------------------------------------------------------------------------
+// Equal-time correlations of local families (dwhmc_corr.hip)
+// ---------------------------------------------------------------------------
+
+// The term table, pair list and reference sites of a correlation call as the
+// device reads them (ints, terms in the caller's order, duplicates kept).
+struct CorrPlan {
+  std::vector<int> tptr, trow, tcol, pairs, ref;
+  std::vector<double2> val;
+};
+constexpr int64_t kCorrMaxTermsAll = 1 << 24;
+constexpr int64_t kCorrMaxPartials = 1 << 27;
+
+// Checks the arguments and fills the plan; with_pairs / with_local: the pair
+// list / the reference sites are needed (else ignored).  ctx may be NULL.
+int corr_plan(dwh_ctx* ctx, int64_t N, int64_t nfam, const int64_t* tptr, const int64_t* trow, const int64_t* tcol,
+              const dwh_c128* tval, bool with_pairs, int64_t npairs, const int64_t* pairs, bool with_local,
+              int64_t nref, const int64_t* ref, CorrPlan* pl) {
+  const std::string pre = "correlations";
+  if (N < 1 || N > (1 << 24)) return fail(ctx, DWH_ERR_ARG, pre + ": N must be in [1, 2^24]");
+  if (2 * N > dwh::kCorrMaxN2)
+    return fail(ctx, DWH_ERR_ARG, pre + ": 2N above " + std::to_string(dwh::kCorrMaxN2));
+  if (nfam < 1 || nfam > (1 << 16)) return fail(ctx, DWH_ERR_ARG, pre + ": nfam must be in [1, 2^16]");
+  if (!tptr) return fail(ctx, DWH_ERR_ARG, pre + ": NULL argument (tptr)");
+  if (tptr[0] != 0) return fail(ctx, DWH_ERR_ARG, pre + ": tptr must start at 0");
+  const int64_t nsl = nfam * N;
+  for (int64_t e = 0; e < nsl; ++e) {
+    const std::string at = "(family " + std::to_string(e / N) + ", site " + std::to_string(e % N) + ")";
+    if (tptr[e + 1] < tptr[e]) return fail(ctx, DWH_ERR_ARG, pre + ": tptr decreases at " + at);
+    if (tptr[e + 1] - tptr[e] > dwh::kCorrMaxTerms)
+      return fail(ctx, DWH_ERR_ARG, pre + ": more than " + std::to_string(dwh::kCorrMaxTerms) + " terms at " + at);
+    if (tptr[e + 1] > kCorrMaxTermsAll) return fail(ctx, DWH_ERR_ARG, pre + ": more than 2^24 terms");
+  }
+  const int64_t nt = tptr[nsl], n2 = 2 * N;
+  if (nt > 0 && (!trow || !tcol || !tval)) return fail(ctx, DWH_ERR_ARG, pre + ": NULL argument (trow, tcol or tval)");
+  for (int64_t t = 0; t < nt; ++t) {
+    if (trow[t] < 0 || trow[t] >= n2 || tcol[t] < 0 || tcol[t] >= n2)
+      return fail(ctx, DWH_ERR_ARG, pre + ": term " + std::to_string(t) + " (" + std::to_string(trow[t]) + ", " +
+                                        std::to_string(tcol[t]) + ") outside [0, 2N)");
+    if (!std::isfinite(tval[t].re) || !std::isfinite(tval[t].im))
+      return fail(ctx, DWH_ERR_ARG, pre + ": non-finite value at term " + std::to_string(t));
+  }
+  if (with_pairs) {
+    if (npairs < 1) return fail(ctx, DWH_ERR_ARG, pre + ": npairs must be >= 1 with a corr or local output");
+    if (!pairs) return fail(ctx, DWH_ERR_ARG, pre + ": NULL argument (pairs)");
+    if (npairs > (1 << 16)) return fail(ctx, DWH_ERR_ARG, pre + ": more than 2^16 pairs");
+    for (int64_t k = 0; k < 2 * npairs; ++k)
+      if (pairs[k] < 0 || pairs[k] >= nfam)
+        return fail(ctx, DWH_ERR_ARG, pre + ": pair index " + std::to_string(pairs[k]) + " outside [0, nfam)");
+  }
+  if (with_local) {
+    if (nref < 1) return fail(ctx, DWH_ERR_ARG, pre + ": a local output needs nref >= 1");
+    if (!ref) return fail(ctx, DWH_ERR_ARG, pre + ": NULL argument (ref)");
+    if (nref > (1 << 16)) return fail(ctx, DWH_ERR_ARG, pre + ": more than 2^16 reference sites");
+    for (int64_t q = 0; q < nref; ++q)
+      if (ref[q] < 0 || ref[q] >= N)
+        return fail(ctx, DWH_ERR_ARG, pre + ": reference site " + std::to_string(ref[q]) + " outside [0, N)");
+  }
+  if (with_pairs &&
+      npairs * N * std::max<int64_t>(dwh::corr_chunks((int)N), with_local ? nref : 0) > kCorrMaxPartials)
+    return fail(ctx, DWH_ERR_ARG, pre + ": more than 2^27 (pair, site, displacement) partials");
+  pl->tptr.assign(tptr, tptr + nsl + 1);
+  pl->trow.assign(trow, trow + nt);
+  pl->tcol.assign(tcol, tcol + nt);
+  pl->val.resize((size_t)nt);
+  for (int64_t t = 0; t < nt; ++t) pl->val[(size_t)t] = make_double2(tval[t].re, tval[t].im);
+  pl->pairs.clear();
+  pl->ref.clear();
+  if (with_pairs) pl->pairs.assign(pairs, pairs + 2 * npairs);
+  if (with_local) pl->ref.assign(ref, ref + nref);
+  return DWH_OK;
+}
+
+// mean, corr and local (host, per state nfam N, npairs N and npairs nref N
+// complex; each nullable) of the m states of src.  Per state S = diag(f) U^H
+// into the slot's JU, ρ = U S into its Jmn (the library's product; it runs
+// for a mean-only call too: the gather reads ρ), then the gather, the
+// contraction with its chunk sum, and the contraction on the reference sites.
+int corr_run(dwh_ctx* ctx, const TrSrc& src, int m, const CorrPlan& pl, int64_t nfam, dwh_c128* mean, dwh_c128* corr,
+             dwh_c128* local) {
+  int rc;
+  if ((rc = transport_prepare(ctx, std::max<int64_t>(ctx->tr_nw, 0), std::max<int64_t>(ctx->tr_nd, 0), m)))
+    return rc;
+  // (the workspace only now: transport_prepare releases it when it grows the slots)
+  const int N = ctx->d.N, n2 = 2 * N, Lx = (int)ctx->model->Lx;
+  const int64_t sA = (int64_t)n2 * n2, nsl = nfam * N, nt = (int64_t)pl.val.size();
+  const int np = (int)(pl.pairs.size() / 2), nref = local ? (int)pl.ref.size() : 0, nc = dwh::corr_chunks(N);
+  const int64_t n_mean = mean ? nsl : 0, n_corr = corr ? (int64_t)np * N : 0, n_loc = (int64_t)np * nref * N;
+  const int64_t o_row = nsl + 1, o_col = o_row + nt, o_pair = o_col + nt, o_ref = o_pair + 2 * np;
+  if ((rc = rs_grow(ctx, &ctx->d_cr_idx, &ctx->cr_nidx, o_ref + (int64_t)pl.ref.size())) ||
+      (rc = rs_grow(ctx, &ctx->d_cr_val, &ctx->cr_nval, nt)) ||
+      (rc = rs_grow(ctx, &ctx->d_cr_part, &ctx->cr_npart, corr ? (int64_t)np * nc * N : 0)) ||
+      (rc = rs_grow(ctx, &ctx->d_cr_out, &ctx->cr_nout, n_mean + n_corr + n_loc)))
+    return rc;
+  hipStream_t s = ctx->stream;
+  auto up = [&](void* dst, const void* p, size_t bytes) {
+    return bytes == 0 ? hipSuccess : hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, s);
+  };
+  int* ix = ctx->d_cr_idx;
+  HIPCHECK(ctx, up(ix, pl.tptr.data(), pl.tptr.size() * sizeof(int)));
+  HIPCHECK(ctx, up(ix + o_row, pl.trow.data(), pl.trow.size() * sizeof(int)));
+  HIPCHECK(ctx, up(ix + o_col, pl.tcol.data(), pl.tcol.size() * sizeof(int)));
+  HIPCHECK(ctx, up(ix + o_pair, pl.pairs.data(), pl.pairs.size() * sizeof(int)));
+  HIPCHECK(ctx, up(ix + o_ref, pl.ref.data(), pl.ref.size() * sizeof(int)));
+  HIPCHECK(ctx, up(ctx->d_cr_val, pl.val.data(), pl.val.size() * sizeof(double2)));
+  HIPCHECK(ctx, hipStreamSynchronize(s));   // (the uploads)
+  if ((rc = eigen_solve(ctx, src, m))) return rc;
+  // bytes the contractions issue: two 16-byte loads per (term of A, term of B)
+  std::vector<double> cnt((size_t)nfam, 0.0);
+  for (int64_t k = 0; k < nfam; ++k) cnt[(size_t)k] = (double)(pl.tptr[(size_t)((k + 1) * N)] - pl.tptr[(size_t)(k * N)]);
+  double issued = 0;
+  for (int p = 0; p < np; ++p) {
+    const int a = pl.pairs[2 * (size_t)p], b = pl.pairs[2 * (size_t)p + 1];
+    if (corr) issued += 32.0 * cnt[(size_t)a] * cnt[(size_t)b];
+    for (int q = 0; q < nref; ++q) {
+      const size_t e = (size_t)b * N + (size_t)pl.ref[(size_t)q];
+      issued += 32.0 * cnt[(size_t)a] * (double)(pl.tptr[e + 1] - pl.tptr[e]);
+    }
+  }
+  const double2 one = make_double2(1.0, 0.0), zero = make_double2(0.0, 0.0);
+  double2 *o_mean = ctx->d_cr_out, *o_corr = o_mean + n_mean, *o_loc = o_corr + n_corr;
+  auto down = [&](dwh_c128* dst, const double2* p, int64_t count) {
+    return hipMemcpyAsync(dst, p, (size_t)count * sizeof(double2), hipMemcpyDeviceToHost, s);
+  };
+  for (int k = 0; k < m; ++k) {
+    const dwh::TrBufs b = tr_slot(ctx, k);
+    double2* rho = b.Jmn;
+    {
+      Scope sc(ctx, T_CORR_RHO, 8.0 * n2 * (double)n2 * n2);
+      dwh::launch_op_fermi(b.E, N, ctx->beta, b.f, b.g, s);
+      dwh::launch_tr_conj_transpose(b.U, n2, n2, n2, 0, b.Jmn, n2, 0, 1, s);
+      dwh::launch_map_fscale(b.Jmn, N, b.f, b.JU, s);
+      dwh::gemm_z('N', 'N', n2, n2, n2, one, b.U, n2, sA, b.JU, n2, sA, zero, rho, n2, sA, 1, s);
+    }
+    if (np > 0 && (corr || local)) {
+      Scope sc(ctx, T_CORR_CONTRACT, issued);
+      if (corr)
+        dwh::launch_corr(rho, N, Lx, ix, ix + o_row, ix + o_col, ctx->d_cr_val, ix + o_pair, np, nullptr, N,
+                         ctx->d_cr_part, s);
+      if (local)
+        dwh::launch_corr(rho, N, Lx, ix, ix + o_row, ix + o_col, ctx->d_cr_val, ix + o_pair, np, ix + o_ref, nref,
+                         o_loc, s);
+    }
+    {
+      Scope sc(ctx, T_CORR_REDUCE, 16.0 * ((double)n_corr * (nc + 1) + (double)n_mean + 2.0 * (mean ? nt : 0)));
+      if (corr) dwh::launch_corr_sum(ctx->d_cr_part, N, np, o_corr, s);
+      if (mean) dwh::launch_corr_mean(rho, N, ix, ix + o_row, ix + o_col, ctx->d_cr_val, (int)nfam, o_mean, s);
+    }
+    HIPCHECK(ctx, hipGetLastError());
+    if (mean) HIPCHECK(ctx, down(mean + (size_t)k * nsl, o_mean, n_mean));
+    if (corr) HIPCHECK(ctx, down(corr + (size_t)k * n_corr, o_corr, n_corr));
+    if (local) HIPCHECK(ctx, down(local + (size_t)k * n_loc, o_loc, n_loc));
+    // (the next state overwrites d_cr_out: the copies are on the same stream)
+  }
+  return eigen_info_check(ctx, m);   // (synchronises)
+}
 
 }  // namespace
 
@@ -1141,6 +1301,51 @@ int dwh_debug_response_map_plan(int64_t N, int64_t npat, const int64_t* prow, co
   if (int rc = map_plan(nullptr, N, npat, prow, pcol, &pl)) return rc;
   std::copy(pl.order.begin(), pl.order.end(), order);
   std::copy(pl.colptr.begin(), pl.colptr.end(), colptr);
+  return DWH_OK;
+}
+
+int dwh_measure_correlations(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta, int64_t nfam,
+                             const int64_t* tptr, const int64_t* trow, const int64_t* tcol, const dwh_c128* tval,
+                             int64_t npairs, const int64_t* pairs, int64_t nref, const int64_t* ref, dwh_c128* mean,
+                             dwh_c128* corr, dwh_c128* local) {
+  if (!ctx) return fail(nullptr, DWH_ERR_ARG, "NULL context");
+  int rc;
+  if ((rc = check_state_args(ctx, chain, nstates, Delta))) return rc;
+  if (!mean && !corr && !local) return fail(ctx, DWH_ERR_ARG, "correlations: mean, corr and local are all NULL");
+  const int64_t N = ctx->d.N;
+  CorrPlan pl;
+  if ((rc = corr_plan(ctx, N, nfam, tptr, trow, tcol, tval, corr || local, npairs, pairs, local != nullptr, nref, ref,
+                      &pl)))
+    return rc;
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  SETTLE(ctx);
+  // DWHMC_RESPONSE_GROUP=g: state groups of at most g (tests of the grouping loop).  Only this call reads
+  // it for its states: the vertex responses spend it on their vertex groups (rs_group).
+  int cap = 0;
+  if (const char* e = std::getenv("DWHMC_RESPONSE_GROUP")) cap = std::max(1, std::atoi(e));
+  const int64_t np = corr || local ? npairs : 0, nr = local ? nref : 0;
+  return for_each_state_group(ctx, chain, nstates, Delta, [&](const TrSrc& src, int m, int64_t s0) {
+    return corr_run(ctx, src, m, pl, nfam, mean ? mean + (size_t)s0 * nfam * N : nullptr,
+                    corr ? corr + (size_t)s0 * np * N : nullptr, local ? local + (size_t)s0 * np * nr * N : nullptr);
+  }, cap);
+}
+
+int dwh_debug_correlation_dense(int64_t N, int64_t nfam, const int64_t* tptr, const int64_t* trow,
+                                const int64_t* tcol, const dwh_c128* tval, int64_t npairs, const int64_t* pairs,
+                                int64_t nref, const int64_t* ref, dwh_c128* out) {
+  if (!out) return fail(nullptr, DWH_ERR_ARG, "correlations: NULL argument (out)");
+  CorrPlan pl;
+  if (int rc = corr_plan(nullptr, N, nfam, tptr, trow, tcol, tval, npairs != 0 || pairs, npairs, pairs,
+                         nref != 0 || ref, nref, ref, &pl))
+    return rc;
+  const size_t n2 = 2 * (size_t)N;
+  std::fill(out, out + (size_t)nfam * N * n2 * n2, dwh_c128{0.0, 0.0});
+  for (size_t e = 0; e < (size_t)(nfam * N); ++e)
+    for (int t = pl.tptr[e]; t < pl.tptr[e + 1]; ++t) {
+      dwh_c128& o = out[e * n2 * n2 + (size_t)pl.trow[(size_t)t] + (size_t)pl.tcol[(size_t)t] * n2];
+      o.re += pl.val[(size_t)t].x;
+      o.im += pl.val[(size_t)t].y;
+    }
   return DWH_OK;
 }
 

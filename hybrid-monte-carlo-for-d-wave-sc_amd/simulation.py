@@ -305,15 +305,60 @@ class ResponseMap(_Option):
         return {"response_map": r["dmap"][k], "rho_map": r["rho"][k]}
 
 
+class Correlations(_Option):
+    """correlations = dict(families=[kind, ...], pairs=[(a, b), ...],
+    ref_sites=[site, ...]) (kind a key of vertices.LOCAL_KINDS, default
+    pair_d_create, built once by vertices.local_family; pairs indices into
+    families, default every (k, k); ref_sites default None: no local output;
+    FermionContext.measure_correlations): the equal-time correlations of local
+    operators.  Each sweep_<i>.npz gains the complex bin means corr ((npairs,
+    Ly, Lx), connected and translation-averaged), corr_mean ((nfam, Ly, Lx),
+    from whose bin mean the disconnected part of the *bin-averaged* means
+    follows; the disconnected part of each sweep needs the per-sweep means)
+    and, with ref_sites, corr_local ((npairs, nref, Ly, Lx));
+    spectra_bins/correlations_pairs.npy holds the pairs."""
+    keyword, keys = "correlations", ("families", "pairs", "ref_sites")
+
+    def __init__(self, raw, p):
+        super().__init__(raw, p)
+        self.names = [str(k) for k in raw.get("families", ["pair_d_create"])]
+        if not self.names:
+            raise ValueError("correlations: families is empty")
+        self.families = [VX.local_family(k, p) for k in self.names]
+        n, pairs = len(self.names), raw.get("pairs")
+        self.pairs = [(k, k) for k in range(n)] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+        if not self.pairs or any(not (0 <= a < n and 0 <= b < n) for a, b in self.pairs):
+            raise ValueError("correlations: pairs must be a non-empty list of family index pairs")
+        ref = raw.get("ref_sites")
+        self.ref_sites = None if ref is None else [int(q) for q in ref]
+        if self.ref_sites is not None and (not self.ref_sites or any(not 0 <= q < p.N for q in self.ref_sites)):
+            raise ValueError("correlations: ref_sites must be a non-empty list of sites in [0, N)")
+        self.squeezed = ("corr", "mean") + (("local",) if self.ref_sites is not None else ())
+        self.header = ("correlations_pairs.npy", np.asarray(self.pairs, dtype=np.int64).reshape(-1, 2))
+
+    def _call(self, ctx, p, chain, deltas):
+        return ctx.measure_correlations(self.families, pairs=self.pairs, ref_sites=self.ref_sites, chain=chain,
+                                        deltas=deltas)
+
+    def bins(self, r, k):
+        out = {"corr": r["corr"][k], "corr_mean": r["mean"][k]}
+        if self.ref_sites is not None:
+            out["corr_local"] = r["local"][k]
+        return out
+
+
 # The drivers' measurement options, in the order of their results in the bins.  A further one is a
 # description here and its keyword in the drivers' and TransportQueue's signatures.
 OPTIONS = (SpectralMaps, CurrentResponse, OperatorResponse, NambuResponse, ResponseMap)
+# The equal-time measurements, taken after OPTIONS.  A tuple of its own only because
+# tests/test_measurement_options.py pins OPTIONS to its five keywords: merging the two waits for that test.
+EQUAL_TIME_OPTIONS = (Correlations,)
 
 
 def parse_options(p, **raw) -> list:
     """The options taken (not None) among the drivers' keywords, parsed, in the
-    order of OPTIONS."""
-    return [o(raw[o.keyword], p) for o in OPTIONS if raw.get(o.keyword) is not None]
+    order of OPTIONS, then of EQUAL_TIME_OPTIONS."""
+    return [o(raw[o.keyword], p) for o in OPTIONS + EQUAL_TIME_OPTIONS if raw.get(o.keyword) is not None]
 
 
 def write_headers(spec_dir: str, p, options=()) -> None:
@@ -339,7 +384,8 @@ class SpectraBins:
     so it does for chi2 ((nops, n_w)) of the operator_response option, the
     complex nambu_chi2 ((npairs, n_w)) of the nambu_response option and the
     complex response_map ((nops, nz, npat)) and rho_map ((npat,)) of the
-    response_map option."""
+    response_map option, and corr, corr_mean and corr_local of the
+    correlations option."""
 
     def __init__(self):
         self.count = 0
@@ -475,18 +521,19 @@ class TransportQueue:
     a batch run as one batched call (dwh_measure_transport_deltas), ~3x the
     throughput of one call per sweep at L = 32.  Rows and bins come out in
     sweep order, each when its batch is measured (batch = 1: right away, as
-    the reference writes them).  The measurement options (OPTIONS; each
+    the reference writes them).  The measurement options (OPTIONS and
+    EQUAL_TIME_OPTIONS; each
     keyword a dict or None) are measured with every batch, each by one call
     batched the same way."""
 
     def __init__(self, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int, chain: int = 0,
                  spectral_maps: dict | None = None, current_response: dict | None = None,
                  operator_response: dict | None = None, nambu_response: dict | None = None,
-                 response_map: dict | None = None):
+                 response_map: dict | None = None, correlations: dict | None = None):
         self._init(ctx, p, out, res, bin_size, batch, chain,
                    parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
                                  operator_response=operator_response, nambu_response=nambu_response,
-                                 response_map=response_map))
+                                 response_map=response_map, correlations=correlations))
 
     @classmethod
     def with_options(cls, options, ctx, p, out: ChainOutput, res: SimulationResult, bin_size: int, batch: int,
@@ -531,7 +578,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
                    cache: H.ComputeCache | None = None, transport_batch: int = 1,
                    spectral_maps: dict | None = None, current_response: dict | None = None,
                    operator_response: dict | None = None,
-                   nambu_response: dict | None = None, response_map: dict | None = None) -> SimulationResult:
+                   nambu_response: dict | None = None, response_map: dict | None = None,
+                   correlations: dict | None = None) -> SimulationResult:
     """src/Simulation.jl:34-236.  Files in out_dir: simulation.log (appended),
     observables.csv, transport.csv (one row per transport measurement, every
     measure_transport_freq sweeps; <= 0 disables), and spectra_bins/ — the
@@ -542,14 +590,15 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
     one batched call (TransportQueue): same rows and bins, written up to
     transport_batch - 1 sweeps later.
     spectral_maps, current_response, operator_response, nambu_response,
-    response_map: the measurement options (OPTIONS), each a dict that its
-    description documents (SpectralMaps, CurrentResponse, OperatorResponse,
-    NambuResponse, ResponseMap) or None (the default): the files as without
+    response_map, correlations: the measurement options (OPTIONS and
+    EQUAL_TIME_OPTIONS), each a dict that its description documents
+    (SpectralMaps, CurrentResponse, OperatorResponse, NambuResponse,
+    ResponseMap, Correlations) or None (the default): the files as without
     the option.  All are checked before any file is opened."""
     rng = rng if rng is not None else np.random.default_rng()
     options = parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
                             operator_response=operator_response, nambu_response=nambu_response,
-                            response_map=response_map)
+                            response_map=response_map, correlations=correlations)
     out = ChainOutput(out_dir, verbose)
     try:
         out.header(p, n_therm, n_measure, measure_transport_freq, bin_size)
@@ -595,7 +644,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                           delta_cap: float = 0.0, transport_batch: int = 1,
                           spectral_maps: dict | None = None, current_response: dict | None = None,
                           operator_response: dict | None = None,
-                          nambu_response: dict | None = None, response_map: dict | None = None) -> list:
+                          nambu_response: dict | None = None, response_map: dict | None = None,
+                          correlations: dict | None = None) -> list:
     """len(out_dirs) independent run_simulation's (src/Simulation.jl:34-236),
     chain k writing out_dirs[k] and drawing from rngs[k] in the reference's
     order (initialize_state, then per sweep randn(ComplexF64) and rand() only
@@ -612,11 +662,12 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
     largest spectral bound over the chains, and a guard trip re-selects it
     for every chain, so dH differs at ~1e-12 and a Metropolis decision can
     differ).  spectral_maps, current_response, operator_response,
-    nambu_response, response_map: as run_simulation's, for every chain."""
+    nambu_response, response_map, correlations: as run_simulation's, for every
+    chain."""
     K = len(out_dirs)
     options = parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
                             operator_response=operator_response, nambu_response=nambu_response,
-                            response_map=response_map)
+                            response_map=response_map, correlations=correlations)
     if len(rngs) != K or K < 1:
         raise ValueError("one rng per output directory")
     outs = [ChainOutput(d, verbose) for d in out_dirs]

@@ -39,6 +39,26 @@ density matrix D(z)[W] and ρ on a pattern of Nambu index pairs (a, b):
     diamagnetic_map,     the local dia_i, Λ_i and stiffness dia_i - Λ_i from ρ and
     paramagnetic_map,    D(0)[J_α(q = 0)]; their site means are the current
     stiffness_map        response's dia, Λ(q = 0, l = 0) and the stiffness
+
+For FermionContext.measure_correlations, the equal-time correlations
+C_AB(r) = (1/N) Σ_j <O_A(j ⊕ r) O_B(j)†>_c of local operators, a `LocalFamily`
+gives every site i its own bilinear O(i) = Σ_t a_t Ψ†_{row_t} Ψ_{col_t} as
+triplets tagged with their owner site:
+
+    local_family         the q = 0 vertex of a NAMBU_KINDS name with every term
+                         owned by the site i of the bond (i, j_b(i)) it was built
+                         from, so Σ_i O(i) = build_nambu(kind, p, 0, 0)
+    local_terms          the term table (tptr, trow, tcol, tval) of a list of families
+    disconnected         (1/N) Σ_j m_A(j ⊕ r) conj(m_B(j)) from the means
+    structure_factor     S(q) = Σ_r e^{-i q·r} C(r)
+
+Phase convention: a family places a bond operator at its owner site, so the
+Fourier transform Σ_r e^{-i q·r} C(r) carries e^{-i q·r_i} per bond where the
+q-vertices above carry the midpoint phase e^{-i q·(r_i + δ_b/2)}: the two
+differ by e^{-i q·δ_b/2} per bond and agree for on-site operators (density,
+spin, pair_s).  S^x S^x is not a Ψ-bilinear (S^x flips one spin, which
+changes the Nambu charge by two); S^z S^z ("spin") stands for it by spin
+rotation symmetry.
 """
 from __future__ import annotations
 
@@ -471,3 +491,82 @@ def stiffness_map(p, pattern, rho, D, direction="x") -> np.ndarray:
     """dia_i - Λ_i: the local superfluid stiffness, whose mean over the sites
     is the stiffness of the lattice-summed calls."""
     return diamagnetic_map(p, pattern, rho, direction) - paramagnetic_map(p, pattern, D, direction)
+
+
+# --------------------------------------------------------------------------
+# local families (FermionContext.measure_correlations)
+# --------------------------------------------------------------------------
+class LocalFamily(NamedTuple):
+    site: np.ndarray       # int64, owner site of each term, in [0, N)
+    row: np.ndarray        # int64, in [0, 2N)
+    col: np.ndarray        # int64, in [0, 2N)
+    val: np.ndarray        # complex128
+
+    def dense(self, N: int) -> np.ndarray:
+        """(N, 2N, 2N): the matrix of O(i) per site, duplicates summed."""
+        W = np.zeros((N, 2 * N, 2 * N), dtype=np.complex128)
+        np.add.at(W, (self.site, self.row, self.col), self.val)
+        return W
+
+
+def local_family(kind: str, p) -> LocalFamily:
+    """The family of the Nambu vertex `kind` (a key of NAMBU_KINDS) at q = 0:
+    its entries, each owned by the site i of the bond (i, j_b(i)) (or of the
+    site term) it was built from.  Every builder above emits its entries in
+    blocks of N, one per site in site order, which is what assigns the owner."""
+    v = build_nambu(kind, p, 0, 0)
+    N = p.N
+    if len(v.row) % N:
+        raise ValueError(f"{kind!r}: entries do not come in per-site blocks")
+    site = np.tile(np.arange(N, dtype=np.int64), len(v.row) // N)
+    return LocalFamily(site, v.row, v.col, v.val)
+
+
+LOCAL_KINDS = tuple(NAMBU_KINDS)
+
+
+def local_terms(families, N: int):
+    """(tptr (nfam N + 1,), trow, tcol, tval) of a list of LocalFamily as
+    dwh_measure_correlations takes them: the terms of family k at site i are
+    tptr[k N + i] .. tptr[k N + i + 1] - 1, in the family's own order inside a
+    site (duplicates kept)."""
+    families = list(families)
+    if not families:
+        raise ValueError("families is empty")
+    ptr, rows, cols, vals = [np.zeros(1, dtype=np.int64)], [], [], []
+    base = 0
+    for f in families:
+        if not isinstance(f, LocalFamily):
+            raise ValueError("families: a list of vertices.LocalFamily")
+        site, r, c, v = (np.asarray(a).ravel() for a in f)
+        if not (len(site) == len(r) == len(c) == len(v)):
+            raise ValueError("LocalFamily: site, row, col and val differ in length")
+        site = site.astype(np.int64)
+        if len(site) and (site.min() < 0 or site.max() >= N):
+            raise ValueError(f"LocalFamily: owner site outside [0, {N})")
+        order = np.argsort(site, kind="stable")
+        ptr.append(base + np.searchsorted(site[order], np.arange(1, N + 1)).astype(np.int64))
+        rows.append(r[order].astype(np.int64))
+        cols.append(c[order].astype(np.int64))
+        vals.append(v[order].astype(np.complex128))
+        base += len(site)
+    cat = np.concatenate
+    return (np.ascontiguousarray(cat(ptr)), np.ascontiguousarray(cat(rows)), np.ascontiguousarray(cat(cols)),
+            np.ascontiguousarray(cat(vals)))
+
+
+def disconnected(p, mean_a, mean_b) -> np.ndarray:
+    """(1/N) Σ_j m_A(j ⊕ r) conj(m_B(j)) at [..., ry, rx] from the means
+    (..., Ly, Lx) of two families (measure_correlations' mean)."""
+    a = np.asarray(mean_a, dtype=np.complex128)
+    b = np.asarray(mean_b, dtype=np.complex128)
+    return np.fft.ifft2(np.fft.fft2(a) * np.conj(np.fft.fft2(b))) / p.N
+
+
+def structure_factor(p, corr) -> np.ndarray:
+    """S(q) = Σ_r e^{-i q·r} C(r), q = 2π (mx/Lx, my/Ly) at [..., my, mx], of
+    corr (..., Ly, Lx)."""
+    c = np.asarray(corr)
+    if c.shape[-2:] != (p.Ly, p.Lx):
+        raise ValueError(f"corr must end in (Ly, Lx) = ({p.Ly}, {p.Lx})")
+    return np.fft.fft2(c)

@@ -182,7 +182,8 @@ int dwh_stream(dwh_ctx* ctx, void** stream);
  * (bit 0 "gj_update", bit 1 "gj_pivot", bit 2 "assemble", bit 3 "contract",
  * bit 4 "step", bit 5 "gj_edge", bit 6 "cr_gemm", bit 7 "cr_inv", bit 8 "cr_inv_side",
  * bit 9 "eig_own", bit 10 "eig_vendor", bit 11 "cr_sparse", bit 12 "spectral",
- * bit 13 "response", bit 14 "operator", bit 15 "nambu", bit 16 "map");
+ * bit 13 "response", bit 14 "operator", bit 15 "nambu", bit 16 "map",
+ * bit 17 "corr_rho", bit 18 "corr_contract", bit 19 "corr_reduce");
  * 0 disables, -1 times everything. */
 int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
 /* name: "gj_update" (rank-128 paired / rank-64 trailing updates),
@@ -202,7 +203,12 @@ int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
  * state), "nambu" (the same for dwh_measure_nambu_response; work = 8·(2N)³
  * flops per vertex per state), "map" (the same for dwh_measure_response_map;
  * work = 8·(2N)³ flops per vertex, for X, plus 8·(2N)³ per (vertex, frequency),
- * per state; 0 without a dmap output), "assemble",
+ * per state; 0 without a dmap output), "corr_rho" / "corr_contract" /
+ * "corr_reduce" (the stages of dwh_measure_correlations after its eigensolve,
+ * one record each per state: S = diag(f) U^H and the product ρ = U S, work =
+ * 8·(2N)³ flops; the contractions of every pair, corr and local, work = the
+ * bytes they issue, 32 per (term of A, term of B); the chunk sums and the
+ * mean gather, work = the bytes they move), "assemble",
  * "contract", "step"; returns total milliseconds, launches and the
  * algorithmic work summed over launches (fp64 flops; HBM bytes for
  * "assemble"). */
@@ -565,6 +571,74 @@ int dwh_debug_response_map_plan(int64_t N, int64_t npat, const int64_t* prow, co
 int dwh_bench_response_map_stages(dwh_ctx* ctx, int64_t reps, int64_t nfreq, double* weight_ms,
                                   double* sample_ms);
 
+/* ---- equal-time correlations C_AB(r) of local operators ------------------
+ * At a fixed Δ the fermions are free, so Wick's theorem gives the equal-time
+ * correlations of fermion bilinears exactly from the density matrix
+ * ρ[x, y] = Σ_n U[x,n] f_n conj(U[y,n]) = <Ψ†_y Ψ_x> (dwh_measure_response_map's
+ * ρ, here in full), Ψ = (c_{i↑}; c†_{i↓}).  A local family A gives every site
+ * i its own bilinear
+ *   O_A(i) = Σ_t a_{i,t} Ψ†_{r(i,t)} Ψ_{c(i,t)},
+ * r, c Nambu indices in [0, 2N) anywhere on the lattice, a complex, any number
+ * of terms per site up to 64 (zero allowed, duplicates allowed).  The nfam
+ * families share one term table: the terms of family k at site i are
+ * tptr[k·N + i] .. tptr[k·N + i + 1] - 1 of (trow, tcol, tval); tptr has
+ * nfam·N + 1 entries, starts at 0 and does not decrease.  For the pairs
+ * (A_p, B_p) = (pairs[2p], pairs[2p+1]) and sites i, j
+ *   m_A(i)     = Σ_t a_{i,t} ρ[c(i,t), r(i,t)]                          = <O_A(i)> up to its constant
+ *   G_AB(i, j) = Σ_{t,u} a_{i,t} conj(b_{j,u}) conj(ρ[r_A(i,t), r_B(j,u)])
+ *                                            (δ[c_A(i,t), c_B(j,u)] - ρ[c_A(i,t), c_B(j,u)])
+ *              = <O_A(i) O_B(j)†> - <O_A(i)><O_B(j)†>,
+ * and with i = j ⊕ r the periodic translation (x_i = (x_j + r_x) mod Lx,
+ * y_i = (y_j + r_y) mod Ly; sites and r indexed y·Lx + x, 0-based):
+ *   corr [r + N·(p + npairs·s)]            = (1/N) Σ_j G_{A_p B_p}(j ⊕ r, j)
+ *   local[r + N·(q + nref·(p + npairs·s))] = G_{A_p B_p}(ref[q] ⊕ r, ref[q])   (no 1/N)
+ *   mean [i + N·(k + nfam·s)]              = m_k(i)
+ * for state s.  The disconnected part (1/N) Σ_j m_A(j ⊕ r) conj(m_B(j)) follows
+ * from mean on the host.  The Monte Carlo mean over Δ of connected plus
+ * disconnected parts is the interacting correlator.
+ * Delta / nstates / chain, every algorithm, one eigensolve per state and "the
+ * context's own Δ is not touched" as in dwh_measure_nambu_response.  Any
+ * output may be NULL, which skips that part; the ρ product runs for a
+ * mean-only call too (the gather reads ρ).
+ * Cost per state: S = diag(f) U^H and one 2N-cubed product ρ = U S on the
+ * library's own MFMA kernel, then per pair the contraction (dwhmc_corr.hip):
+ * for a fixed j a lane per displacement r, so the rows the lanes of a stencil
+ * family read are neighbours in the column-major ρ; a workgroup takes 256
+ * displacements and 16 sites j in ascending order, and a second kernel adds
+ * the chunks in ascending order.  local is the same kernel on the reference
+ * sites without the sum.  Correctness does not depend on locality or on equal
+ * term counts, only speed does.  States run in the groups of the other
+ * state-list calls; DWHMC_RESPONSE_GROUP=g, which elsewhere bounds the
+ * vertices per group, here bounds the states per group (this call has no
+ * vertex groups; the other calls' state groups ignore it).  ρ takes the measurement
+ * slots' own matrices; the term table, partials and outputs are allocated on
+ * first use, grown on demand and freed with the other response workspaces.
+ * Every sum has a fixed order and no atomics: two calls give the same bits, a
+ * batch of snapshots equals its single-state calls, smaller groups give the
+ * same bits.
+ * DWH_ERR_ARG, nothing launched: everything dwh_measure_nambu_response refuses
+ * for its states, nfam < 1 (or > 2^16), a NULL or decreasing tptr or
+ * tptr[0] != 0, NULL trow / tcol / tval with terms, an index outside [0, 2N),
+ * a non-finite value, more than 64 terms at one (family, site), more than 2^24
+ * terms in all, with a corr or local output npairs < 1 (or > 2^16), NULL pairs
+ * or a pair index outside [0, nfam), with a local output nref < 1 (or > 2^16),
+ * NULL ref or a reference site outside [0, N), more than 2^27 (pair, site,
+ * displacement) partials, all three outputs NULL, 2N > 8192. */
+int dwh_measure_correlations(dwh_ctx* ctx, int64_t chain, int64_t nstates, const dwh_c128* Delta,
+                             int64_t nfam, const int64_t* tptr, const int64_t* trow, const int64_t* tcol,
+                             const dwh_c128* tval, int64_t npairs, const int64_t* pairs,
+                             int64_t nref, const int64_t* ref,
+                             dwh_c128* mean, dwh_c128* corr, dwh_c128* local);
+/* Host only (no device, no context): the validation above and the terms as
+ * uploaded, expanded into out: nfam·N dense 2N x 2N column-major matrices,
+ * one per (family, site) at out + (k·N + i)·(2N)², duplicates summed.  The
+ * pair list is checked as for a corr output when npairs != 0 or pairs is not
+ * NULL, the reference sites as for a local output when nref != 0 or ref is
+ * not NULL.  Errors as above, the text where dwh_last_error(NULL) reads it. */
+int dwh_debug_correlation_dense(int64_t N, int64_t nfam, const int64_t* tptr, const int64_t* trow,
+                                const int64_t* tcol, const dwh_c128* tval, int64_t npairs,
+                                const int64_t* pairs, int64_t nref, const int64_t* ref, dwh_c128* out);
+
 /* ---- assembly read-back (parity tests; not on the hot path) -------------
  * The BdG matrix H_BdG(Δ) exactly as the device assembles it, so tests can
  * compare it bit-for-bit with init_static_H! + update_H_BdG!
@@ -595,8 +669,9 @@ int dwh_debug_qeig(dwh_ctx* ctx, int64_t chain, double* E, double* ms);
  * (U need not diagonalise anything).  The next eigensolve of this context
  * with exactly nstates matrices — the one dwh_measure_transport(_deltas),
  * dwh_measure_spectral_maps, dwh_measure_current_response,
- * dwh_measure_operator_response, dwh_measure_nambu_response and
- * dwh_measure_response_map run after preparing their buffers — copies
+ * dwh_measure_operator_response, dwh_measure_nambu_response,
+ * dwh_measure_response_map and dwh_measure_correlations run after preparing
+ * their buffers — copies
  * them into its slots instead of solving, reports the solve as particle-hole
  * closed (dwh_info_t::eig_half) iff ph != 0 and as not structure-preserving
  * (eig_quat = 0), and clears the staging: the injection is one-shot.  With

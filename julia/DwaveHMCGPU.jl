@@ -335,6 +335,34 @@ function measure_response_map(cache::GPUCache, p::ModelParameters, rowptr::Vecto
     return ρ, D
 end
 
+# Equal-time correlations for the Δ the context holds (dwh_measure_correlations):
+# local families O_A(i) = Σ_t a Ψ†_r Ψ_c as one term table — the terms of family
+# k at site i are tptr[k N + i + 1] + 1 : tptr[k N + i + 2] of (trow, tcol, tval),
+# tptr, trow, tcol 0-based as the ABI takes them — and `pairs` (2 x npairs,
+# 0-based family indices).  Returns (mean, corr, local): mean[i + 1, k + 1] =
+# <O_k(i)>, corr[r + 1, p + 1] = (1/N) Σ_j G_p(j ⊕ r, j) and local[r + 1, q + 1,
+# p + 1] = G_p(ref_q ⊕ r, ref_q) with G_AB(i, j) = <O_A(i) O_B(j)†> -
+# <O_A(i)><O_B(j)†>; `ref` (0-based sites) empty skips local.  Not run; the same
+# ABI call is exercised through ctypes by tests/test_correlations.py.
+function measure_correlations(cache::GPUCache, p::ModelParameters, tptr::Vector{Int64}, trow::Vector{Int64},
+                              tcol::Vector{Int64}, tval::Vector{ComplexF64}, pairs::Matrix{Int64};
+                              ref::Vector{Int64}=Int64[])
+    (length(tptr) - 1) % p.N == 0 || throw(ArgumentError("tptr must have nfam N + 1 entries"))
+    size(pairs, 1) == 2 || throw(ArgumentError("pairs must be 2 x npairs"))
+    nfam, npairs, nref = (length(tptr) - 1) ÷ p.N, size(pairs, 2), length(ref)
+    m = zeros(ComplexF64, p.N, nfam)
+    c = zeros(ComplexF64, p.N, npairs)
+    l = zeros(ComplexF64, p.N, nref, npairs)
+    GC.@preserve tptr trow tcol tval pairs ref m c l check(cache.ctx, ccall((:dwh_measure_correlations, libdwhmc), Cint,
+                           (Ptr{Cvoid}, Int64, Int64, Ptr{ComplexF64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
+                            Ptr{ComplexF64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{ComplexF64},
+                            Ptr{ComplexF64}, Ptr{ComplexF64}),
+                           cache.ctx, 0, 1, C_NULL, nfam, pointer(tptr), pointer(trow), pointer(tcol), pointer(tval),
+                           npairs, pointer(pairs), nref, nref > 0 ? pointer(ref) : C_NULL, pointer(m), pointer(c),
+                           nref > 0 ? pointer(l) : C_NULL))
+    return m, c, l
+end
+
 # ---------------------------------------------------------------------------
 # run_simulation on the GPU.  The reference constructs its cache inside the
 # driver (`cache = initialize_cache(p)`, src/Simulation.jl:82), so the driver
