@@ -20,8 +20,8 @@ from .hmc import (ComputeCache, ModelParameters, ObservablesResult, SimulationSt
                   initialize_cache, initialize_state, measure_observables, neighbour_tables,
                   refresh_momentum, standard_complex_normal, update_H_BdG, SpectrumResult,
                   measure_transport_and_spectra)
-from .context import (FermionContext, debug_cr_launch, debug_current_vertex, selftest_mfma, spectral_window,
-                      transport_grid)
+from .context import (OMELYAN2_LAMBDA, FermionContext, debug_cr_launch, debug_current_vertex, integrator_schedule,
+                      selftest_mfma, spectral_window, transport_grid)
 from .simulation import AdaptiveNt, SimulationResult, run_simulation, run_simulation_chains
 from . import vertices
 from ._lib import DwhError, SpectrumGuardError, lib_path, load as load_library
@@ -33,5 +33,6 @@ __all__ = [
     "refresh_momentum", "standard_complex_normal", "update_H_BdG", "FermionContext", "selftest_mfma",
     "DwhError", "SpectrumGuardError", "lib_path", "load_library", "AdaptiveNt", "SimulationResult",
     "run_simulation", "run_simulation_chains", "SpectrumResult", "measure_transport_and_spectra", "transport_grid",
-    "spectral_window", "debug_cr_launch", "debug_current_vertex", "vertices",
+    "spectral_window", "debug_cr_launch", "debug_current_vertex", "vertices", "integrator_schedule",
+    "OMELYAN2_LAMBDA",
 ]

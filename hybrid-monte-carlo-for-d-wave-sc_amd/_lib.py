@@ -74,6 +74,9 @@ SIGNATURES = {
     "dwh_hmc_sweep": (C.c_int, [_P, _P, _P, _I64, _D, _D, _P, _P]),
     "dwh_hmc_trajectory": (C.c_int, [_P, _P, _I64, _D, _D, _P]),
     "dwh_hmc_finish": (C.c_int, [_P, _P]),
+    "dwh_set_integrator": (C.c_int, [_P, _I32, _D, _I64, _P, _P]),
+    "dwh_get_integrator": (C.c_int, [_P, C.POINTER(_I32), _DP, C.POINTER(_I64), _P, _P]),
+    "dwh_debug_integrator_schedule": (C.c_int, [_I32, _D, _I64, _P, _P, _I64, _D, _D, C.POINTER(_I64), _P, _P]),
     "dwh_load_draws": (C.c_int, [_P, _I64, _P, _P]),
     "dwh_run_sweeps": (C.c_int, [_P, _I64, _I64, _I64, _D, _D]),
     "dwh_sweep_results": (C.c_int, [_P, _I64, _I64, _P, _P]),

@@ -41,6 +41,53 @@ def table_to_abi(table: np.ndarray) -> np.ndarray:
 # β·E'/2 is beyond the pole table
 ALGOS = {"auto": -1, "dense": 0, "cr": 1, "eig": 2}
 
+# HMC integrators (include/dwhmc.h DWH_INT_*, DWH_OMELYAN2_LAMBDA)
+INTEGRATORS = {"leapfrog": 0, "omelyan2": 1, "custom": 2}
+_INTEGRATOR_NAMES = {v: k for k, v in INTEGRATORS.items()}
+OMELYAN2_LAMBDA = 0.1931833275037836
+MAX_STAGES = 16
+
+
+def _integrator_args(kind, lam, kick, drift):
+    """(kind code, λ, S, kick array, drift array) as the ABI takes them; the
+    arrays only for "custom", whose S is the drift's length.  The library
+    checks the schedule itself."""
+    if kind not in INTEGRATORS:
+        raise ValueError(f"integrator kind must be one of {sorted(INTEGRATORS)}")
+    if kind != "custom":
+        if kick is not None or drift is not None:
+            raise ValueError(f"integrator {kind}: kick and drift belong to kind='custom'")
+        return INTEGRATORS[kind], float(lam), 0, None, None
+    a = None if kick is None else np.ascontiguousarray(np.asarray(kick, dtype=np.float64).reshape(-1))
+    b = None if drift is None else np.ascontiguousarray(np.asarray(drift, dtype=np.float64).reshape(-1))
+    if a is not None and b is not None and len(a) != len(b) + 1:
+        raise ValueError("integrator custom: kick has one entry more than drift (a_0..a_S, b_1..b_S)")
+    S = len(b) if b is not None else len(a) - 1 if a is not None else 0
+    return INTEGRATORS[kind], float(lam), S, a, b
+
+
+def integrator_stages(kind="leapfrog", kick=None, drift=None) -> int:
+    """Force evaluations (factorisations) per step of an integrator."""
+    return {"leapfrog": 1, "omelyan2": 2}.get(kind) or _integrator_args(kind, 0.0, kick, drift)[2]
+
+
+def integrator_schedule(kind, Nt: int, dt: float, mass: float, lam: float = OMELYAN2_LAMBDA, kick=None, drift=None,
+                        nstage: int | None = None, lib=None):
+    """(kicks, drifts) of a trajectory of Nt steps as the enqueue hands them to
+    the kick/drift kernels (dwh_debug_integrator_schedule; host arithmetic, no
+    device): S·Nt + 1 kicks and S·Nt drifts, leapfrog at Nt = 0 its two half
+    kicks.  nstage overrides the S taken from the arrays' lengths.  ValueError
+    for what the library refuses."""
+    lib = _lib.load() if lib is None else lib
+    k, lam, S, a, b = _integrator_args(kind, lam, kick, drift)
+    S = S if nstage is None else int(nstage)
+    args = (k, lam, S, ptr(a), ptr(b), int(Nt), float(dt), float(mass))
+    nfact = C.c_int64()
+    check(lib.dwh_debug_integrator_schedule(*args, C.byref(nfact), None, None))
+    kicks, drifts = np.empty(max(nfact.value + 1, 2)), np.empty(nfact.value)
+    check(lib.dwh_debug_integrator_schedule(*args, C.byref(nfact), ptr(kicks), ptr(drifts)))
+    return kicks[:nfact.value + 1 if nfact.value else 2], drifts
+
 
 class FermionContext:
     """Device-resident fermionic action/force evaluator for nchains chains.
@@ -168,6 +215,26 @@ class FermionContext:
         if a.shape != (self.nchains,):
             raise ValueError("one accept flag per chain")
         self._c(self._lib.dwh_hmc_finish(self._h, ptr(a)))
+
+    def set_integrator(self, kind="omelyan2", lam: float = OMELYAN2_LAMBDA, kick=None, drift=None):
+        """The splitting every trajectory of this context runs from now on
+        (dwh_set_integrator): "leapfrog" (the default of a new context),
+        "omelyan2" (two factorisations per step, `lam` its λ) or "custom" with
+        kick = a_0..a_S and drift = b_1..b_S.  Nt stays the number of steps, so
+        a trajectory makes S·Nt factorisations.  ValueError for a schedule the
+        library refuses."""
+        k, lam, S, a, b = _integrator_args(kind, lam, kick, drift)
+        self._c(self._lib.dwh_set_integrator(self._h, k, lam, S, ptr(a), ptr(b)))
+
+    @property
+    def integrator(self) -> dict:
+        """dwh_get_integrator: kind, lam (0 unless omelyan2), and the kick
+        (S + 1) and drift (S) coefficients in use."""
+        kind, lam, S = C.c_int32(), C.c_double(), C.c_int64()
+        a, b = np.zeros(MAX_STAGES + 1), np.zeros(MAX_STAGES)
+        self._c(self._lib.dwh_get_integrator(self._h, C.byref(kind), C.byref(lam), C.byref(S), ptr(a), ptr(b)))
+        return dict(kind=_INTEGRATOR_NAMES[kind.value], lam=lam.value, kick=a[:S.value + 1].copy(),
+                    drift=b[:S.value].copy())
 
     # -- throughput path -------------------------------------------------
     def load_draws(self, noise, uniform):

@@ -252,27 +252,42 @@ void fermion_energy_enqueue(dwh_ctx* ctx) {
                                ctx->beta, ctx->Ef, ctx->Trhh, ctx->stream);
 }
 
+// Nt against the context's integrator (Nt = 0 is leapfrog's alone), with the
+// reason for dwh_last_error
+int trajectory_args(dwh_ctx* ctx, int64_t Nt, double dt, double mass) {
+  dwh::FlatSchedule f;
+  std::string why;
+  if (dwh::flatten_schedule(ctx->integ, Nt, dt, mass, &f, &why) != DWH_OK) return fail(ctx, DWH_ERR_ARG, why);
+  return DWH_OK;
+}
+
 // One hmc_sweep! trajectory reading its draws from device pointers
-// (src/HMC.jl:71-122): refresh, H_old, backup, leapfrog, H_new.
+// (src/HMC.jl:71-122): refresh, H_old, backup, the integrator, H_new.
+// The integrator is the context's splitting (dwhmc_integrator.h) flattened
+// into one (kick, drift) pair per launch; leapfrog, the default, gives the
+// reference's 0.5 dt, dt, ..., 0.5 dt kicks and dt / 2m drifts (:91-118).  The
+// caller has checked Nt against the integrator (trajectory_args).
 // with_hnew = false: the caller's k_traj_end forms H_new (with the Metropolis test)
 void trajectory_enqueue(dwh_ctx* ctx, const double2* noise, int64_t Nt, double dt, double mass,
                         bool with_hnew = true, const dwh::SweepHalt& sh = dwh::SweepHalt{}) {
   const Dims& d = ctx->d;
   hipStream_t s = ctx->stream;
-  const double coef_field = dt / (2.0 * mass);                                        // :95
-  // :77 refresh, :80 H_old, :84-86 backup, :91-92 half kick fused with step
-  // 1's drift (:101): one launch (k_traj_begin)
+  dwh::FlatSchedule f;
+  if (dwh::flatten_schedule(ctx->integ, Nt, dt, mass, &f, nullptr) != DWH_OK) return;
+  const int64_t n = f.nfact;
+  // :77 refresh, :80 H_old, :84-86 backup, :91-92 first kick fused with the
+  // first drift (:101): one launch (k_traj_begin)
   dwh::launch_traj_begin(d, noise, std::sqrt(2.0 * mass), ctx->Pi, ctx->Delta, ctx->Pair, ctx->F, ctx->Ef,
                          ctx->Trhh, ctx->DeltaB, ctx->PairB, ctx->EfB, ctx->TrhhB, ctx->Hold, ctx->beta, ctx->J,
-                         mass, kickdrift(ctx, 0.5 * dt, Nt > 0 ? coef_field : 0.0), sh, s);
-  for (int64_t step = 1; step <= Nt; ++step) {                                        // :98
-    // :105-107 update_H_BdG! + diagonalize + compute_forces!, then the kick of
-    // :111-113 (dt) and the next step's drift (:101), or the final half kick
-    // of :118 on the last step
-    factorize_enqueue(ctx, step < Nt ? kickdrift(ctx, dt, coef_field) : kickdrift(ctx, 0.5 * dt, 0.0));
+                         mass, kickdrift(ctx, f.kick(0), n > 0 ? f.drift(0) : 0.0), sh, s);
+  for (int64_t i = 1; i <= n; ++i) {                                                  // :98
+    // :105-107 update_H_BdG! + diagonalize + compute_forces!, then the kick
+    // after this force evaluation (:111-113) and the next drift (:101), or
+    // the final kick of :118 after the last one
+    factorize_enqueue(ctx, kickdrift(ctx, f.kick(i), i < n ? f.drift(i) : 0.0));
   }
-  if (Nt <= 0)
-    dwh::launch_force_from_pair(d, ctx->Pair, ctx->Delta, ctx->F, ctx->Pi, kickdrift(ctx, 0.5 * dt, 0.0),
+  if (n <= 0)
+    dwh::launch_force_from_pair(d, ctx->Pair, ctx->Delta, ctx->F, ctx->Pi, kickdrift(ctx, f.kick(1), 0.0),
                                 ctx->beta, ctx->J, s);
   else
     fermion_energy_enqueue(ctx);
@@ -665,6 +680,7 @@ int reselect_poles(dwh_ctx* ctx, double new_cap) {
   std::copy(ctx->t_n, ctx->t_n + T_COUNT, n->t_n);
   std::copy(ctx->t_work, ctx->t_work + T_COUNT, n->t_work);
   n->reselections = ctx->reselections + 1;
+  n->integ = ctx->integ;   // dwh_set_integrator's setting outlives the pole set
   // the context keeps its stream (a handle from dwh_stream stays valid); the
   // new device side's stream goes with the old one
   (void)hipStreamSynchronize(n->stream);
@@ -893,6 +909,7 @@ int dwh_hmc_sweep(dwh_ctx* ctx, const dwh_c128* noise, const double* uniform, in
                   double mass, uint8_t* accepted, double* dH) {
   if (!ctx || !noise || !uniform || !accepted || !dH) return fail(ctx, DWH_ERR_ARG, "NULL argument");
   if (Nt < 0 || !(mass > 0) || !std::isfinite(dt)) return fail(ctx, DWH_ERR_ARG, "bad Nt/dt/mass");
+  if (int rc = trajectory_args(ctx, Nt, dt, mass)) return rc;
   if (ctx->pending) return fail(ctx, DWH_ERR_STATE, "dwh_hmc_finish the pending trajectory first");
   HIPCHECK(ctx, hipSetDevice(ctx->device));
   if (!ctx->enq.empty())
@@ -922,6 +939,7 @@ int dwh_hmc_trajectory(dwh_ctx* ctx, const dwh_c128* noise, int64_t Nt, double d
                        double* dH) {
   if (!ctx || !noise || !dH) return fail(ctx, DWH_ERR_ARG, "NULL argument");
   if (Nt < 0 || !(mass > 0) || !std::isfinite(dt)) return fail(ctx, DWH_ERR_ARG, "bad Nt/dt/mass");
+  if (int rc = trajectory_args(ctx, Nt, dt, mass)) return rc;
   if (ctx->pending) return fail(ctx, DWH_ERR_STATE, "dwh_hmc_finish the pending trajectory first");
   HIPCHECK(ctx, hipSetDevice(ctx->device));
   if (!ctx->enq.empty())
@@ -964,6 +982,33 @@ int dwh_hmc_finish(dwh_ctx* ctx, const uint8_t* accepted) {
   HIPCHECK(ctx, hipGetLastError());
   HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->pending = false;
+  return DWH_OK;
+}
+
+int dwh_set_integrator(dwh_ctx* ctx, int32_t kind, double lambda, int64_t nstage, const double* kick,
+                       const double* drift) {
+  if (!ctx) return DWH_ERR_ARG;
+  if (ctx->pending) return fail(ctx, DWH_ERR_STATE, "dwh_hmc_finish the pending trajectory first");
+  dwh::Integrator integ;
+  std::string why;
+  if (dwh::make_integrator(kind, lambda, nstage, kick, drift, &integ, &why) != DWH_OK)
+    return fail(ctx, DWH_ERR_ARG, why);
+  HIPCHECK(ctx, hipSetDevice(ctx->device));
+  // enqueued throughput sweeps run, and after a guard trip replay, with the
+  // schedule they were enqueued under
+  SETTLE(ctx);
+  ctx->integ = integ;
+  return DWH_OK;
+}
+
+int dwh_get_integrator(dwh_ctx* ctx, int32_t* kind, double* lambda, int64_t* nstage, double* kick, double* drift) {
+  if (!ctx) return DWH_ERR_ARG;
+  const dwh::Integrator& g = ctx->integ;
+  if (kind) *kind = g.kind;
+  if (lambda) *lambda = g.lambda;
+  if (nstage) *nstage = g.stages();
+  if (kick) std::copy(g.kick.begin(), g.kick.end(), kick);
+  if (drift) std::copy(g.drift.begin(), g.drift.end(), drift);
   return DWH_OK;
 }
 
@@ -1026,6 +1071,7 @@ int dwh_run_sweeps(dwh_ctx* ctx, int64_t first, int64_t nsweeps, int64_t Nt, dou
   if (first < 0 || nsweeps < 0 || first + nsweeps > ctx->ndraws)
     return fail(ctx, DWH_ERR_ARG, "sweep range outside the loaded draws");
   if (Nt < 0 || !(mass > 0)) return fail(ctx, DWH_ERR_ARG, "bad Nt/mass");
+  if (int rc = trajectory_args(ctx, Nt, dt, mass)) return rc;
   if (ctx->pending) return fail(ctx, DWH_ERR_STATE, "dwh_hmc_finish the pending trajectory first");
   HIPCHECK(ctx, hipSetDevice(ctx->device));
   const Dims& d = ctx->d;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/dwhmc.h"
+#include "dwhmc_integrator.h"
 #include "dwhmc_internal.h"
 #include "dwhmc_model.h"
 #include "dwhmc_plan.h"
@@ -91,6 +92,9 @@ struct dwh_ctx {
     double dt, mass;
   };
   std::vector<EnqSweep> enq;   // throughput sweeps enqueued since the last settle()
+  // the splitting every trajectory runs (dwh_set_integrator; default leapfrog);
+  // it changes only with `enq` empty, so a replay runs what was enqueued
+  dwh::Integrator integ;
   // draws / results: single-sweep scratch (s_*) and the throughput path
   double2* s_noise = nullptr;
   double* s_uniform = nullptr;

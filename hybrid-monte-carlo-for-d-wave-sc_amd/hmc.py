@@ -177,18 +177,22 @@ def standard_complex_normal(rng: np.random.Generator, shape) -> np.ndarray:
 
 def hmc_sweep(cache: ComputeCache, p: ModelParameters, state: SimulationState, *, Nt: int, dt: float,
               rng: np.random.Generator | None = None, noise: np.ndarray | None = None,
-              uniform: float | None = None):
+              uniform: float | None = None, integrator: dict | None = None):
     """src/HMC.jl:71-144.  Draws come from `rng` unless injected.  With `rng`
     and no injected uniform, the Metropolis uniform is drawn only when
     ΔH >= 0 — the short-circuit of src/HMC.jl:128 — so the generator is
     consumed exactly as the reference consumes its own (dwh_hmc_trajectory +
-    dwh_hmc_finish).  Returns (accepted, ΔH); mutates state.Δ, state.π and
-    the cache."""
+    dwh_hmc_finish).  integrator: None (the context's, leapfrog unless set
+    before) or the keywords of FermionContext.set_integrator, which the
+    context keeps from this sweep on; Nt stays the number of steps.  Returns
+    (accepted, ΔH); mutates state.Δ, state.π and the cache."""
     ctx = cache.require()
     if rng is None and (noise is None or uniform is None):
         # checked before any device call: a missing generator must not leave
         # a trajectory pending on the context
         raise ValueError("hmc_sweep needs `rng` unless both noise and uniform are injected")
+    if integrator is not None:
+        ctx.set_integrator(**integrator)
     if noise is None:
         noise = standard_complex_normal(rng, (p.N, 2))
     ctx.set_state(state.Delta, None)

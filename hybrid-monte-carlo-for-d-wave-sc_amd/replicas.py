@@ -53,6 +53,9 @@ class ReplicaConfig:
     Nt: int = 10
     seed: int = 1000
     transport_freq: int = 0   # measure_transport_and_spectra every k sweeps (0: never)
+    # FermionContext.set_integrator's keywords (kind, lam, kick, drift), or None: the context's leapfrog;
+    # Nt stays the number of steps
+    integrator: dict | None = None
 
 
 def replica_seed(cfg: ReplicaConfig, rank: int, chain: int) -> int:
@@ -78,6 +81,8 @@ def run_local(p, cfg: ReplicaConfig, rank: int, device: int, make_context, initi
     ctx = make_context(np.stack(dis))
     ctx.set_pairing(np.stack(D0))
     ctx.factorize()                                        # src/Simulation.jl:84-86
+    if cfg.integrator is not None:
+        ctx.set_integrator(**cfg.integrator)
     dt = calc_optimal_dt(p.beta, p.J, p.mass, cfg.Nt)
     out = np.zeros((cfg.n_sweeps, cfg.chains, N_OBS))
     for s in range(cfg.n_sweeps):

@@ -26,7 +26,7 @@ import numpy as np
 
 from . import hmc as H
 from . import vertices as VX
-from .context import spectral_window, transport_grid
+from .context import integrator_schedule, spectral_window, transport_grid
 
 OBS_HEADER = ("Sweep,Accepted,dH,Energy,Delta_Amp,Delta_Loc,Delta_Glob,S_Delta,Hole_p,Delta_Diff,"
               "Delta_Pair,Delta_LocalPair")
@@ -43,10 +43,13 @@ def obs_csv_line(sweep: int, acc: bool, dH: float, obs: H.ObservablesResult) -> 
 @dataclass
 class AdaptiveNt:
     """Thermalisation step-count controller, src/Simulation.jl:103-129: every
-    `window` sweeps, acceptance < 0.60 -> Nt += 2; > 0.95 and Nt > 4 -> Nt -= 1."""
+    `window` sweeps, acceptance < 0.60 -> Nt += 2; > 0.95 and Nt > Nt_min ->
+    Nt -= 1 (Nt_min = 4 is the reference's; an integrator that conserves
+    energy with fewer steps lowers it, Integrator)."""
     Nt: int
     window: int = 5
     recent: int = 0
+    Nt_min: int = 4
 
     def record(self, i: int, accepted: bool):
         """Sweep i (1-based) finished.  Returns None between windows, else
@@ -60,7 +63,7 @@ class AdaptiveNt:
         old = self.Nt
         if rate < 0.60:
             self.Nt += 2
-        elif rate > 0.95 and self.Nt > 4:
+        elif rate > 0.95 and self.Nt > self.Nt_min:
             self.Nt -= 1
         return rate, old, self.Nt
 
@@ -361,6 +364,44 @@ def parse_options(p, **raw) -> list:
     return [o(raw[o.keyword], p) for o in OPTIONS + EQUAL_TIME_OPTIONS if raw.get(o.keyword) is not None]
 
 
+class Integrator:
+    """integrator = a name ("leapfrog", "omelyan2") or dict(kind=, lam=, kick=,
+    drift=, Nt_min=): the splitting of every trajectory of the run
+    (FermionContext.set_integrator's keywords; kind default "omelyan2") and the
+    lower bound of the adaptive thermalisation's Nt (default 4, the
+    reference's; >= 1).  Nt_therm_init and Nt_measure stay numbers of steps, so
+    a trajectory makes stages·Nt factorisations.  The schedule is checked by
+    the library's own rule (integrator_schedule, no device) when parsed;
+    simulation.log records it and the factorisations per trajectory.  None,
+    the drivers' default: no call, no log line, every file as without it."""
+    keys = ("kind", "lam", "kick", "drift", "Nt_min")
+
+    def __init__(self, raw):
+        raw = dict(kind=raw) if isinstance(raw, str) else dict(raw)
+        extra = set(raw) - set(self.keys)
+        if extra:
+            raise ValueError(f"integrator: unknown keys {sorted(extra)}")
+        self.Nt_min = int(raw.pop("Nt_min", 4))
+        if self.Nt_min < 1:
+            raise ValueError("integrator: Nt_min >= 1")
+        self.args = {k: v for k, v in raw.items() if v is not None}
+        self.args.setdefault("kind", "omelyan2")
+        kicks, _ = integrator_schedule(Nt=1, dt=1.0, mass=1.0, **self.args)
+        self.stages = len(kicks) - 1
+
+    def apply(self, ctx, out) -> None:
+        """onto a context, with the log line of what the context then holds"""
+        ctx.set_integrator(**self.args)
+        g = ctx.integrator
+        lam = f" lam={g['lam']!r}" if g["kind"] == "omelyan2" else ""
+        out.tee(f"Integrator: {g['kind']}{lam}, {self.stages} factorisations per step, "
+                f"kick={[float(a) for a in g['kick']]}, drift={[float(b) for b in g['drift']]}, Nt_min={self.Nt_min}")
+
+
+def parse_integrator(integrator):
+    return None if integrator is None else Integrator(integrator)
+
+
 def write_headers(spec_dir: str, p, options=()) -> None:
     """jldsave(params, omega_grid) of src/Simulation.jl:89 as params.json and
     omega_grid.npy, and the options' header files."""
@@ -474,10 +515,10 @@ class ChainOutput:
             f.close()
 
 
-def thermalize(cache, p, state, out: ChainOutput, n_therm: int, Nt_therm_init: int, rng):
+def thermalize(cache, p, state, out: ChainOutput, n_therm: int, Nt_therm_init: int, rng, Nt_min: int = 4):
     """The adaptive thermalisation of src/Simulation.jl:92-130 for one chain;
     returns (final Nt, acceptance rate)."""
-    ctl = AdaptiveNt(Nt_therm_init)
+    ctl = AdaptiveNt(Nt_therm_init, Nt_min=Nt_min)
     dt = H.calc_optimal_dt(p.beta, p.J, p.mass, ctl.Nt)
     out.tee("--- Thermalization Start ---")
     out.tee(f"Init: Nt={ctl.Nt}, dt={round(dt, 5)}")
@@ -579,7 +620,7 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
                    spectral_maps: dict | None = None, current_response: dict | None = None,
                    operator_response: dict | None = None,
                    nambu_response: dict | None = None, response_map: dict | None = None,
-                   correlations: dict | None = None) -> SimulationResult:
+                   correlations: dict | None = None, integrator=None) -> SimulationResult:
     """src/Simulation.jl:34-236.  Files in out_dir: simulation.log (appended),
     observables.csv, transport.csv (one row per transport measurement, every
     measure_transport_freq sweeps; <= 0 disables), and spectra_bins/ — the
@@ -594,11 +635,15 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
     EQUAL_TIME_OPTIONS), each a dict that its description documents
     (SpectralMaps, CurrentResponse, OperatorResponse, NambuResponse,
     ResponseMap, Correlations) or None (the default): the files as without
-    the option.  All are checked before any file is opened."""
+    the option.  integrator: the trajectories' splitting and the adaptive
+    Nt's lower bound (Integrator), a name, a dict or None (the default: the
+    reference's leapfrog, the files as without the keyword).  All are checked
+    before any file is opened."""
     rng = rng if rng is not None else np.random.default_rng()
     options = parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
                             operator_response=operator_response, nambu_response=nambu_response,
                             response_map=response_map, correlations=correlations)
+    integ = parse_integrator(integrator)
     out = ChainOutput(out_dir, verbose)
     try:
         out.header(p, n_therm, n_measure, measure_transport_freq, bin_size)
@@ -611,11 +656,16 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         H.diagonalize_H_BdG(cache, p)
         if measure_transport_freq > 0:
             write_headers(out.spec_dir, p, options)
-        Nt_fin, acc_th = thermalize(cache, p, state, out, n_therm, Nt_therm_init, rng)
+        if integ is not None:
+            integ.apply(cache.require(), out)
+        Nt_fin, acc_th = thermalize(cache, p, state, out, n_therm, Nt_therm_init, rng,
+                                    Nt_min=4 if integ is None else integ.Nt_min)
 
         dt_meas = H.calc_optimal_dt(p.beta, p.J, p.mass, Nt_measure)
         out.tee("--- Measurement Start ---")
         out.tee(f"Settings: Nt={Nt_measure}, dt={round(dt_meas, 5)}")
+        if integ is not None:
+            out.tee(f"Factorisations per trajectory: {integ.stages * Nt_measure}")
         t1 = time.time()
         acc_total = 0
         res = SimulationResult(Nt_fin, acc_th, 0.0)
@@ -645,7 +695,7 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                           spectral_maps: dict | None = None, current_response: dict | None = None,
                           operator_response: dict | None = None,
                           nambu_response: dict | None = None, response_map: dict | None = None,
-                          correlations: dict | None = None) -> list:
+                          correlations: dict | None = None, integrator=None) -> list:
     """len(out_dirs) independent run_simulation's (src/Simulation.jl:34-236),
     chain k writing out_dirs[k] and drawing from rngs[k] in the reference's
     order (initialize_state, then per sweep randn(ComplexF64) and rand() only
@@ -662,12 +712,13 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
     largest spectral bound over the chains, and a guard trip re-selects it
     for every chain, so dH differs at ~1e-12 and a Metropolis decision can
     differ).  spectral_maps, current_response, operator_response,
-    nambu_response, response_map, correlations: as run_simulation's, for every
-    chain."""
+    nambu_response, response_map, correlations, integrator: as
+    run_simulation's, for every chain."""
     K = len(out_dirs)
     options = parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
                             operator_response=operator_response, nambu_response=nambu_response,
                             response_map=response_map, correlations=correlations)
+    integ = parse_integrator(integrator)
     if len(rngs) != K or K < 1:
         raise ValueError("one rng per output directory")
     outs = [ChainOutput(d, verbose) for d in out_dirs]
@@ -682,7 +733,10 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
             H.diagonalize_H_BdG(cache, p)
             if measure_transport_freq > 0:
                 write_headers(outs[k].spec_dir, p, options)
-            Nt_fin, acc_th = thermalize(cache, p, st, outs[k], n_therm, Nt_therm_init, rngs[k])
+            if integ is not None:
+                integ.apply(cache.require(), outs[k])
+            Nt_fin, acc_th = thermalize(cache, p, st, outs[k], n_therm, Nt_therm_init, rngs[k],
+                                        Nt_min=4 if integ is None else integ.Nt_min)
             cache.ctx.close()
             states.append(st)
             results.append(SimulationResult(Nt_fin, acc_th, 0.0))
@@ -693,10 +747,14 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
         try:
             ctx.set_pairing(np.stack([st.Delta for st in states]))
             ctx.factorize()
+            if integ is not None:
+                ctx.set_integrator(**integ.args)
             dt_meas = H.calc_optimal_dt(p.beta, p.J, p.mass, Nt_measure)
             for o in outs:
                 o.tee("--- Measurement Start ---")
                 o.tee(f"Settings: Nt={Nt_measure}, dt={round(dt_meas, 5)}")
+                if integ is not None:
+                    o.tee(f"Factorisations per trajectory: {integ.stages * Nt_measure}")
             t1 = time.time()
             acc_total = np.zeros(K, dtype=np.int64)
             tqs = [TransportQueue.with_options(options, ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k)

@@ -158,6 +158,55 @@ int dwh_hmc_trajectory(dwh_ctx* ctx, const dwh_c128* noise, int64_t Nt, double d
                        double* dH);
 int dwh_hmc_finish(dwh_ctx* ctx, const uint8_t* accepted);
 
+/* The integrator of a context's trajectories (dwh_hmc_sweep,
+ * dwh_hmc_trajectory, dwh_run_sweeps).  One step of size dt is a symmetric
+ * splitting with S >= 1 force evaluations (factorisations):
+ *   kick a_0·dt;  for s = 1..S: drift b_s·dt, force evaluation, kick a_s·dt
+ * with kick π += c·F and drift Δ += c/(2m)·π, the two updates of
+ * [src/HMC.jl:92,101,112,118].  Nt steps are concatenated with the adjacent
+ * end and start kicks merged into one of (a_S + a_0)·dt, so a trajectory
+ * makes S·Nt factorisations; Nt keeps its meaning (steps) in every entry
+ * point, and the "step" timer counts factorisations.
+ *   DWH_INT_LEAPFROG  S = 1, a = (1/2, 1/2), b = (1): the reference's
+ *                     integrator [src/HMC.jl:88-118] and the default, bit for
+ *                     bit what a context without this call runs; the only
+ *                     one that takes Nt = 0 (two half kicks, no factorisation);
+ *   DWH_INT_OMELYAN2  S = 2, a = (λ, 1 - 2λ, λ), b = (1/2, 1/2), 0 < λ < 1/2:
+ *                     the second-order minimum-norm scheme at
+ *                     λ = DWH_OMELYAN2_LAMBDA (Omelyan, Mryglod, Folk, Comput.
+ *                     Phys. Commun. 151 (2003) 272); the optimum in λ is sharp
+ *                     (DESIGN.md §4i), so pass that value unless exploring;
+ *   DWH_INT_CUSTOM    kick = a_0..a_S (nstage + 1 entries), drift = b_1..b_S
+ *                     (nstage entries), 1 <= nstage <= 16: all finite, Σa = 1
+ *                     and Σb = 1 within 1e-12, palindromic bit for bit
+ *                     (a_s = a_{S-s}, b_s = b_{S+1-s}).
+ * lambda is read by OMELYAN2 only; nstage, kick and drift by CUSTOM only.
+ * Pending throughput sweeps are settled first, so a batch never mixes
+ * schedules; the setting survives pole re-selections.  DWH_ERR_STATE between
+ * dwh_hmc_trajectory and dwh_hmc_finish; DWH_ERR_ARG for a schedule that
+ * breaks a rule above (the context keeps its integrator). */
+enum { DWH_INT_LEAPFROG = 0, DWH_INT_OMELYAN2 = 1, DWH_INT_CUSTOM = 2 };
+#define DWH_OMELYAN2_LAMBDA 0.1931833275037836
+int dwh_set_integrator(dwh_ctx* ctx, int32_t kind, double lambda, int64_t nstage, const double* kick,
+                       const double* drift);
+/* The context's integrator: kind and lambda as set (lambda 0 unless
+ * OMELYAN2), nstage = S and the coefficients in use, presets included (kick:
+ * S + 1 entries, drift: S; at most 17 and 16).  Every output may be NULL. */
+int dwh_get_integrator(dwh_ctx* ctx, int32_t* kind, double* lambda, int64_t* nstage, double* kick,
+                       double* drift);
+/* Host only, no device: the coefficients a trajectory of Nt steps of the
+ * given integrator hands to the kick/drift kernels, from the function the
+ * enqueue itself calls.  nfact = S·Nt; kicks_out: nfact + 1 entries, the
+ * first with the momentum refresh, entry i after factorisation i, in units of
+ * F (merged kicks as one double); drifts_out: nfact entries, entry i before
+ * factorisation i + 1, b·dt/(2 mass) in units of π.  Leapfrog with Nt = 0:
+ * nfact = 0 and kicks_out gets the two half kicks.  Every output may be NULL
+ * (nfact alone sizes the others).  DWH_ERR_ARG as dwh_set_integrator and the
+ * trajectory entry points refuse (dwh_last_error(NULL)). */
+int dwh_debug_integrator_schedule(int32_t kind, double lambda, int64_t nstage, const double* kick,
+                                  const double* drift, int64_t Nt, double dt, double mass, int64_t* nfact,
+                                  double* kicks_out, double* drifts_out);
+
 /* Throughput path: upload the draws of nsweeps sweeps once (noise:
  * nsweeps*nchains*2N, uniform: nsweeps*nchains), then enqueue sweeps that
  * read them from HBM without host round trips.  A guard trip inside a batch

@@ -129,6 +129,29 @@ function hmc_sweep!(cache::GPUCache, p::ModelParameters, state::SimulationState;
     return accepted, ΔH
 end
 
+# The integrator of every later hmc_sweep! on this cache (dwh_set_integrator,
+# include/dwhmc.h): :leapfrog (the reference's, src/HMC.jl:88-118, and the
+# default without this call), :omelyan2 (two factorisations per step; λ its
+# parameter, default the minimum-norm value) or :custom with kick = a_0..a_S
+# and drift = b_1..b_S.  Nt of hmc_sweep! stays the number of steps.  Call it
+# after init_static_H! (which creates the context).  Like the rest of this
+# file it has not been run (no Julia in this image); the entry it binds is
+# exercised through ctypes by tests/test_integrator_gpu.py.
+const OMELYAN2_LAMBDA = 0.1931833275037836
+function set_integrator!(cache::GPUCache, kind::Symbol=:omelyan2; λ::Float64=OMELYAN2_LAMBDA,
+                         kick::Vector{Float64}=Float64[], drift::Vector{Float64}=Float64[])
+    code = kind === :leapfrog ? Int32(0) : kind === :omelyan2 ? Int32(1) : kind === :custom ? Int32(2) :
+           throw(ArgumentError("integrator kind must be :leapfrog, :omelyan2 or :custom"))
+    kind === :custom && length(kick) != length(drift) + 1 &&
+        throw(ArgumentError("custom integrator: kick has one entry more than drift"))
+    GC.@preserve kick drift check(cache.ctx, ccall((:dwh_set_integrator, libdwhmc), Cint,
+                                                   (Ptr{Cvoid}, Int32, Float64, Int64, Ptr{Float64}, Ptr{Float64}),
+                                                   cache.ctx, code, λ, length(drift),
+                                                   kind === :custom ? pointer(kick) : C_NULL,
+                                                   kind === :custom ? pointer(drift) : C_NULL))
+    return nothing
+end
+
 # src/Observables.jl:88-222 from what the factorisation caches instead of the
 # eigenpairs: E_f (dwh_fermion_energy, = -Σ_{E>0}(βE + 2 log1pexp(-βE)) of
 # :147-156), P_ij (dwh_pairing, the ρ sums of :172-198) and Tr ρ_hh

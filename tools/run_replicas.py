@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1000)
     ap.add_argument("--transport-freq", type=int, default=0,
                     help="measure transport every k sweeps (0: never) -> transport.csv")
+    ap.add_argument("--integrator", choices=["leapfrog", "omelyan2"], default=None,
+                    help="the trajectories' splitting (default: the context's leapfrog); --Nt stays steps")
     ap.add_argument("--out", default="runs/replicas")
     a = ap.parse_args()
 
@@ -55,7 +57,8 @@ def main():
 
     p = m.ModelParameters(a.L, a.L, 1.0, -0.35, -1.08, 1.0, 0.05, a.beta, 0.8, 1.0)
     cfg = rep.ReplicaConfig(chains=a.chains, n_sweeps=a.sweeps, Nt=a.Nt, seed=a.seed,
-                            transport_freq=a.transport_freq)
+                            transport_freq=a.transport_freq,
+                            integrator=None if a.integrator is None else dict(kind=a.integrator))
 
     def make_context(disorder):
         return m.FermionContext(p.Lx, p.Ly, p.t, p.tp, p.mu, p.beta, p.J, p.nn_table, p.nnn_table,
