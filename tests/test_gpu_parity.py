@@ -6,7 +6,11 @@ spectrum, the strict one to <= 2e-14):
   * pairing P_ij    ‖P_gpu - P_ref‖∞ ≤ 1e-11
   * E_f             |ΔE_f| ≤ 1e-11 |E_f|
   * hole density    |Δ hole_conc| ≤ 1e-11
-  * HMC sweep       |ΔdH| ≤ 1e-8 (1 + |dH|), Δ after the sweep ≤ 1e-10, accept flag equal
+  * HMC sweep       |ΔdH| ≤ 1e-8 (1 + |dH|), Δ after the sweep ≤ 1e-10, π ≤ 1e-9, accept flag equal
+  * after a sweep   the cache of the kept state (tests/test_hmc_chains.py): P ≤ 1e-11,
+                    |ΔE_f| ≤ 1e-11 |E_f|, |Δ Tr ρ_hh| ≤ 1e-11 N (test_cr_bp128_matches_dense_L64's) — the
+                    factorisation bars, since an accepted chain's cache is the last factorisation's and a
+                    rejected chain's a copy
 The oracle restates the reference with LAPACK zheevr (oracle/dwhmc_oracle.py).
 """
 import math
