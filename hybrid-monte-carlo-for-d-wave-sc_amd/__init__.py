@@ -20,7 +20,7 @@ from .hmc import (ComputeCache, ModelParameters, ObservablesResult, SimulationSt
                   initialize_cache, initialize_state, measure_observables, neighbour_tables,
                   refresh_momentum, standard_complex_normal, update_H_BdG, SpectrumResult,
                   measure_transport_and_spectra)
-from .context import (OMELYAN2_LAMBDA, FermionContext, debug_cr_launch, debug_current_vertex, integrator_schedule,
+from .context import (OBS_LOG_FIELDS, OMELYAN2_LAMBDA, FermionContext, sweep_log_layout, debug_cr_launch, debug_current_vertex, integrator_schedule,
                       selftest_mfma, spectral_window, transport_grid)
 from .simulation import AdaptiveNt, SimulationResult, run_simulation, run_simulation_chains
 from . import vertices
@@ -34,5 +34,5 @@ __all__ = [
     "DwhError", "SpectrumGuardError", "lib_path", "load_library", "AdaptiveNt", "SimulationResult",
     "run_simulation", "run_simulation_chains", "SpectrumResult", "measure_transport_and_spectra", "transport_grid",
     "spectral_window", "debug_cr_launch", "debug_current_vertex", "vertices", "integrator_schedule",
-    "OMELYAN2_LAMBDA",
+    "OMELYAN2_LAMBDA", "OBS_LOG_FIELDS", "sweep_log_layout",
 ]

@@ -80,6 +80,11 @@ SIGNATURES = {
     "dwh_load_draws": (C.c_int, [_P, _I64, _P, _P]),
     "dwh_run_sweeps": (C.c_int, [_P, _I64, _I64, _I64, _D, _D]),
     "dwh_sweep_results": (C.c_int, [_P, _I64, _I64, _P, _P]),
+    "dwh_sweep_log": (C.c_int, [_P, _I32, _I64, _I64]),
+    "dwh_sweep_observables": (C.c_int, [_P, _I64, _I64, _P]),
+    "dwh_sweep_field_sq": (C.c_int, [_P, _I64, _I64, _P]),
+    "dwh_sweep_snapshots": (C.c_int, [_P, _I64, _I64, C.POINTER(_I64), _P, _P]),
+    "dwh_sweep_log_layout": (C.c_int, [_I64, _I64, _I64, _I32, _I64, _I64, _I64, _I64, _P]),
     "dwh_synchronize": (C.c_int, [_P]),
     "dwh_stream": (C.c_int, [_P, C.POINTER(_P)]),
     "dwh_timing_enable": (C.c_int, [_P, _I32]),

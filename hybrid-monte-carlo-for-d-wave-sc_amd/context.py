@@ -47,6 +47,30 @@ _INTEGRATOR_NAMES = {v: k for k, v in INTEGRATORS.items()}
 OMELYAN2_LAMBDA = 0.1931833275037836
 MAX_STAGES = 16
 
+# the sweep log (include/dwhmc.h DWH_LOG_*, DWH_OBS_FIELDS): the parts and the
+# columns of the observables record
+LOG_OBS, LOG_FIELD_SQ, LOG_SNAPSHOT = 1, 2, 4
+OBS_LOG_FIELDS = ("total_energy", "Delta_amp", "Delta_local", "Delta_global", "S_Delta", "hole_conc", "Delta_diff",
+                  "Delta_pair", "Delta_localpair", "E_fermion", "tr_hh", "sum_abs2_Delta")
+
+
+def sweep_log_layout(nchains: int, N: int, ndraws: int, observables=True, field_sq=False, snapshot_every=0,
+                     snapshot_offset=0, first=0, nsweeps=None, what=None, lib=None):
+    """(doubles of observables, doubles of field_sq, snapshots) of the sweeps
+    [first, first + nsweeps) of a log over ndraws loaded sweeps
+    (dwh_sweep_log_layout; host arithmetic, no device).  `what` overrides the
+    mask the three switches give.  ValueError for what dwh_sweep_log and the
+    readers refuse."""
+    lib = _lib.load() if lib is None else lib
+    if what is None:
+        what = (LOG_OBS if observables else 0) | (LOG_FIELD_SQ if field_sq else 0)
+        what |= LOG_SNAPSHOT if snapshot_every else 0
+    nsweeps = ndraws - first if nsweeps is None else nsweeps
+    counts = np.zeros(3, dtype=np.int64)
+    check(lib.dwh_sweep_log_layout(int(nchains), int(N), int(ndraws), int(what), int(snapshot_every),
+                                   int(snapshot_offset), int(first), int(nsweeps), ptr(counts)))
+    return tuple(int(c) for c in counts)
+
 
 def _integrator_args(kind, lam, kick, drift):
     """(kind code, λ, S, kick array, drift array) as the ABI takes them; the
@@ -253,6 +277,42 @@ class FermionContext:
         dH = np.zeros((nsweeps, self.nchains))
         self._c(self._lib.dwh_sweep_results(self._h, int(first), int(nsweeps), ptr(acc), ptr(dH)))
         return acc.astype(bool), dH
+
+    def sweep_log(self, observables: bool = True, field_sq: bool = False, snapshot_every: int = 0,
+                  snapshot_offset: int = 0):
+        """What every sweep of run_sweeps records on the device from now on
+        (dwh_sweep_log): the observables record (OBS_LOG_FIELDS), the pairing
+        field's structure factors, and Δ after the sweeps snapshot_offset +
+        k·snapshot_every of the loaded draws (snapshot_every = 0: none).
+        Nothing enabled frees the log.  The buffers start from zero."""
+        what = (LOG_OBS if observables else 0) | (LOG_FIELD_SQ if field_sq else 0)
+        what |= LOG_SNAPSHOT if snapshot_every else 0
+        self._c(self._lib.dwh_sweep_log(self._h, what, int(snapshot_every), int(snapshot_offset)))
+
+    def sweep_observables(self, first: int, nsweeps: int) -> np.ndarray:
+        """(nsweeps, nchains, 12): the record of every chain after the sweeps
+        first .. first + nsweeps - 1, columns OBS_LOG_FIELDS."""
+        out = np.empty((nsweeps, self.nchains, len(OBS_LOG_FIELDS)))
+        self._c(self._lib.dwh_sweep_observables(self._h, int(first), int(nsweeps), ptr(out)))
+        return out
+
+    def sweep_field_sq(self, first: int, nsweeps: int) -> np.ndarray:
+        """(nsweeps, nchains, 2, Ly, Lx): S_d (channel 0) and S_s (1) of the
+        pairing field after every sweep, indexed [ky, kx]."""
+        Lx, Ly = self.info_lattice
+        out = np.empty((nsweeps, self.nchains, 2, Ly, Lx))
+        self._c(self._lib.dwh_sweep_field_sq(self._h, int(first), int(nsweeps), ptr(out)))
+        return out
+
+    def sweep_snapshots(self, first: int, nsweeps: int):
+        """(sweeps (m,), Delta (m, nchains, N, 2)): the snapshots taken after
+        the sweeps of [first, first + nsweeps), ascending."""
+        m = C.c_int64()
+        self._c(self._lib.dwh_sweep_snapshots(self._h, int(first), int(nsweeps), C.byref(m), None, None))
+        sweeps = np.empty(m.value, dtype=np.int64)
+        D = np.empty((m.value, self.nchains, 2, self.N), dtype=np.complex128)
+        self._c(self._lib.dwh_sweep_snapshots(self._h, int(first), int(nsweeps), C.byref(m), ptr(sweeps), ptr(D)))
+        return sweeps, np.ascontiguousarray(np.transpose(D, (0, 1, 3, 2)))
 
     def synchronize(self):
         self._c(self._lib.dwh_synchronize(self._h))
@@ -591,7 +651,7 @@ class FermionContext:
     # -- timing ----------------------------------------------------------
     TIMERS =("gj_update", "gj_pivot", "assemble", "contract", "step", "gj_edge", "cr_gemm", "cr_inv",
               "cr_inv_side", "eig_own", "eig_vendor", "cr_sparse", "spectral", "response", "operator",
-              "nambu", "map", "corr_rho", "corr_contract", "corr_reduce")
+              "nambu", "map", "corr_rho", "corr_contract", "corr_reduce", "sweep_log")
 
     def timing_enable(self, on=True):
         """on: True (all timers), False, or an iterable of timer names."""

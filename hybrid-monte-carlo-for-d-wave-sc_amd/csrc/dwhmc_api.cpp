@@ -675,6 +675,7 @@ int reselect_poles(dwh_ctx* ctx, double new_cap) {
   ctx->acc = nullptr;
   ctx->dH = nullptr;
   ctx->ndraws = 0;
+  dwh::sweep_log_move(ctx, n);
   n->timing = ctx->timing;
   std::copy(ctx->t_ms, ctx->t_ms + T_COUNT, n->t_ms);
   std::copy(ctx->t_n, ctx->t_n + T_COUNT, n->t_n);
@@ -753,6 +754,7 @@ void enqueue_logged(dwh_ctx* ctx, int64_t sw, int64_t Nt, double dt, double mass
   ctx->enq.push_back({sw, Nt, dt, mass});
   sweep_enqueue(ctx, ctx->noise + nbond * sw, ctx->uniform + (size_t)d.nc * sw, ctx->acc + (size_t)d.nc * sw,
                 ctx->dH + (size_t)d.nc * sw, Nt, dt, mass, sh);
+  if (ctx->log_what) dwh::sweep_log_enqueue(ctx, sw);
 }
 
 }  // namespace
@@ -1056,8 +1058,10 @@ int dwh_load_draws(dwh_ctx* ctx, int64_t nsweeps, const dwh_c128* noise, const d
     ctx->uniform = un;
     ctx->acc = ac;
     ctx->dH = dh;
+    ctx->ndraws = nsweeps;
+    // the log grows with the draws and starts from zero
+    if (int rc2 = dwh::sweep_log_resize(ctx)) return rc2;
   }
-  ctx->ndraws = std::max<int64_t>(ctx->ndraws, nsweeps);
   HIPCHECK(ctx, hipMemcpyAsync(ctx->noise, noise, nbond * nsweeps * sizeof(double2),
                                hipMemcpyHostToDevice, ctx->stream));
   HIPCHECK(ctx, hipMemcpyAsync(ctx->uniform, uniform, (size_t)d.nc * nsweeps * sizeof(double),

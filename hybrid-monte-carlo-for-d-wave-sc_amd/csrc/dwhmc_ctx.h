@@ -25,7 +25,7 @@ namespace dwh {
 enum TimerName {
   T_GJ_UPDATE = 0, T_GJ_PIVOT, T_ASSEMBLE, T_CONTRACT, T_STEP, T_GJ_EDGE, T_CR_GEMM, T_CR_INV, T_CR_INVSIDE,
   T_EIG_OWN, T_EIG_VENDOR, T_CR_SPARSE, T_SPECTRAL, T_RESPONSE, T_OPERATOR, T_NAMBU, T_MAP,
-  T_CORR_RHO, T_CORR_CONTRACT, T_CORR_REDUCE, T_COUNT
+  T_CORR_RHO, T_CORR_CONTRACT, T_CORR_REDUCE, T_SWEEP_LOG, T_COUNT
 };
 inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assemble", "contract",
                                                  "step",      "gj_edge",  "cr_gemm",  "cr_inv",
@@ -39,7 +39,8 @@ inline const char* const kTimerNames[T_COUNT] = {"gj_update", "gj_pivot", "assem
                                                  "map",         // response maps after their eigensolve (work: flops)
                                                  "corr_rho",       // correlations: ρ = U f U^H (work: flops)
                                                  "corr_contract",  // ... the Wick contractions (work: bytes issued)
-                                                 "corr_reduce"};   // ... chunk sums and the mean gather (work: bytes)
+                                                 "corr_reduce",    // ... chunk sums and the mean gather (work: bytes)
+                                                 "sweep_log"};     // the sweep log's launches (work: bytes written)
 
 enum Algo { ALGO_DENSE = 0, ALGO_CR = 1, ALGO_EIG = 2 };
 
@@ -105,6 +106,14 @@ struct dwh_ctx {
   double* uniform = nullptr;
   uint8_t* acc = nullptr;
   double* dH = nullptr;
+  // the sweep log (dwh_sweep_log, dwhmc_sweeplog.cpp): which parts every
+  // throughput sweep records (DWH_LOG_* bits), the snapshot cadence, and the
+  // buffers, sized for log_ndraws sweeps (obs: 12 per (sweep, chain); sq: 2 N
+  // per (sweep, chain); snap: Δ per snapshot slot)
+  int32_t log_what = 0;
+  int64_t log_every = 1, log_offset = 0, log_ndraws = 0;
+  double *log_obs = nullptr, *log_sq = nullptr;
+  double2* log_snap = nullptr;
   std::vector<void*> allocations;
 
   // block cyclic-reduction path (algo == ALGO_CR)
@@ -341,6 +350,13 @@ inline void drain_timing(dwh_ctx* ctx) {
   ctx->recs.clear();
 }
 
+// dwhmc_sweeplog.cpp: the log's launches of throughput sweep sw (after
+// launch_traj_end; nothing when no part is enabled); its buffers sized for
+// ctx->ndraws and zero-filled (no-op when the log is off); setting and buffers
+// handed from ctx to the new device side n of a pole re-selection
+void sweep_log_enqueue(dwh_ctx* ctx, int64_t sw);
+int sweep_log_resize(dwh_ctx* ctx);
+void sweep_log_move(dwh_ctx* ctx, dwh_ctx* n);
 // dwhmc_measure.cpp, called from the step and creation code as well:
 // device buffers (+ the rocBLAS handle) of `slots` measurement slots
 int transport_prepare(dwh_ctx* ctx, int64_t nw, int64_t nd, int slots);

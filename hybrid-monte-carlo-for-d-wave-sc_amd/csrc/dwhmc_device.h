@@ -152,6 +152,17 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+// fixed-order sum over a block of 256 threads: wave sums, then the 4 partials
+// in order (red: 4 doubles of LDS); every thread gets the result
+__device__ __forceinline__ double block_sum256(double v, double* red) {
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  v = wave_sum(v);
+  if (l == 0) red[w] = v;
+  __syncthreads();
+  const double t = red[0] + red[1] + red[2] + red[3];
+  __syncthreads();
+  return t;
+}
 
 // 16x16 complex block in one wave: lane l holds row l>>2, columns (l&3)*4..+3.
 // Row p and column p are exchanged through a per-wave LDS scratch (xb: 16

@@ -306,6 +306,21 @@ void launch_restore(const Dims& d, const uint8_t* accepted, const double2* Delta
                     double2* Delta, double2* Pair, double* Ef, double* Trhh, hipStream_t s);
 void launch_sum_ld(const Dims& d, const double* ldpart, double* ldsum, hipStream_t s);
 
+// The sweep log (dwhmc_sweeplog.hip): extra launches after launch_traj_end of
+// a throughput sweep, each returning at once when halt[0] != 0 (SweepHalt).
+// obs: kObsFields doubles per chain from Δ, P, E_f, Tr ρ_hh (DWH_OBS_FIELDS);
+// field_sq: S_d(q), S_s(q) of the pairing field, 2 N doubles per chain, one
+// workgroup per (chain, channel) with 2 N double2 of dynamic LDS, so
+// N <= kLogSqMaxN (non-zero return otherwise, nothing launched); snapshot: Δ
+// of every chain copied to out.
+constexpr int kObsFields = 12;
+constexpr int kLogSqMaxN = 4096;
+void launch_log_obs(const Dims& d, const double2* Delta, const double2* Pair, const double* Ef, const double* Trhh,
+                    double beta, double J, double* out, const int* halt, hipStream_t s);
+int launch_log_field_sq(const Dims& d, int Lx, int Ly, const double2* Delta, double* out, const int* halt,
+                        hipStream_t s);
+void launch_log_snapshot(const Dims& d, const double2* Delta, double2* out, const int* halt, hipStream_t s);
+
 // Transport / spectra measurement (dwhmc_transport.hip): device buffers of one
 // measurement (n2 = 2N; U, JU, Jmn: n2 x n2 column-major)
 struct TrBufs {

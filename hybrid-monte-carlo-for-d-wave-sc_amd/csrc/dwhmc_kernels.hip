@@ -768,16 +768,6 @@ __global__ void k_restore(const uint8_t* __restrict__ accepted, const double2* _
 //          first drift (:91-92, :101)
 //   end:   H_new (:122), Metropolis (:124-129), restore on rejection (:130-141)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum256(double v, double* red) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  v = wave_sum(v);
-  if (l == 0) red[w] = v;
-  __syncthreads();
-  const double t = red[0] + red[1] + red[2] + red[3];
-  __syncthreads();
-  return t;
-}
-
 __global__ __launch_bounds__(256) void k_traj_begin(const double2* __restrict__ noise, double scale,
                                                     double2* __restrict__ Pi, double2* __restrict__ Delta,
                                                     const double2* __restrict__ Pair, double2* __restrict__ F,

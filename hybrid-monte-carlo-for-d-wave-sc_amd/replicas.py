@@ -56,6 +56,10 @@ class ReplicaConfig:
     # FermionContext.set_integrator's keywords (kind, lam, kick, drift), or None: the context's leapfrog;
     # Nt stays the number of steps
     integrator: dict | None = None
+    # None: one hmc_sweep call per sweep.  B >= 1: the throughput path in batches of up to B sweeps, the
+    # records and the transport snapshots logged on the device (FermionContext.sweep_log); same draws, so the
+    # same Markov chains, the records equal up to the summation order of the observables
+    sweep_batch: int | None = None
 
 
 def replica_seed(cfg: ReplicaConfig, rank: int, chain: int) -> int:
@@ -85,6 +89,10 @@ def run_local(p, cfg: ReplicaConfig, rank: int, device: int, make_context, initi
         ctx.set_integrator(**cfg.integrator)
     dt = calc_optimal_dt(p.beta, p.J, p.mass, cfg.Nt)
     out = np.zeros((cfg.n_sweeps, cfg.chains, N_OBS))
+    if cfg.sweep_batch is not None:
+        run_batches(ctx, p, cfg, rngs, dt, out, transport_out)
+        ctx.close()
+        return out
     for s in range(cfg.n_sweeps):
         noise = np.stack([(r.standard_normal((p.N, 2)) + 1j * r.standard_normal((p.N, 2))) * math.sqrt(0.5)
                           for r in rngs])
@@ -104,6 +112,39 @@ def run_local(p, cfg: ReplicaConfig, rank: int, device: int, make_context, initi
                                            for r in spec]))
     ctx.close()
     return out
+
+
+def run_batches(ctx, p, cfg: ReplicaConfig, rngs, dt: float, out: np.ndarray, transport_out: list | None) -> None:
+    """run_local's sweeps in batches of up to cfg.sweep_batch on the throughput
+    path: the draws of a batch in run_local's order (per sweep and chain the
+    noise, then the uniform), the records from the device's sweep log, the
+    transport at the logged Δ snapshots."""
+    B = int(cfg.sweep_batch)
+    if B < 1:
+        raise ValueError("sweep_batch must be at least 1 (or None)")
+    tf = cfg.transport_freq if cfg.transport_freq > 0 and transport_out is not None else 0
+    for done in range(0, cfg.n_sweeps, B):
+        b = min(B, cfg.n_sweeps - done)
+        noise = np.empty((b, cfg.chains, p.N, 2), dtype=np.complex128)
+        uni = np.empty((b, cfg.chains))
+        for s in range(b):
+            for c, r in enumerate(rngs):
+                noise[s, c] = (r.standard_normal((p.N, 2)) + 1j * r.standard_normal((p.N, 2))) * math.sqrt(0.5)
+            uni[s] = [r.random() for r in rngs]
+        ctx.load_draws(noise, uni)
+        ctx.sweep_log(observables=True, snapshot_every=tf, snapshot_offset=(tf - 1 - done) % tf if tf else 0)
+        ctx.run_sweeps(0, b, cfg.Nt, dt, p.mass)
+        acc, dH = ctx.sweep_results(0, b)
+        out[done:done + b, :, 0] = acc
+        out[done:done + b, :, 1] = dH
+        out[done:done + b, :, 2:] = ctx.sweep_observables(0, b)[:, :, :N_OBS - 2]
+        if tf:
+            sweeps, snaps = ctx.sweep_snapshots(0, b)
+            for m, s in enumerate(sweeps):
+                spec = [ctx.measure_transport_deltas(snaps[m, c][None], p.eta, p.domega, p.omega_max, chain=c)[0]
+                        for c in range(cfg.chains)]
+                transport_out.append(np.array([[done + s + 1, r["superfluid_stiffness"], r["dc_conductivity"]]
+                                               for r in spec]))
 
 
 def gather_observables(local: np.ndarray, dist=None, device=None):

@@ -590,6 +590,10 @@ class TransportQueue:
         self.bin_size, self.batch, self.chain = bin_size, max(1, int(batch)), chain
         self.options = options
         self.pending = []            # (sweep, Δ snapshot)
+        # batch = 1 measures at the device Δ, which is the snapshot's when add()
+        # follows its sweep at once; a caller whose device has moved on since
+        # (the sweep-batch drivers) clears this
+        self.at_device = True
 
     def add(self, sweep: int, Delta):
         self.pending.append((sweep, np.array(Delta, dtype=np.complex128, copy=True)))
@@ -600,7 +604,7 @@ class TransportQueue:
         if not self.pending:
             return
         p = self.p
-        if self.batch == 1:
+        if self.batch == 1 and self.at_device:
             deltas = None
             specs = [self.ctx.measure_transport(p.eta, p.domega, p.omega_max, chain=self.chain)]
         else:
@@ -612,6 +616,74 @@ class TransportQueue:
         self.pending = []
 
 
+def measure_in_batches(ctx, p, outs, results, rngs, tqs, *, n_measure: int, Nt: int, dt: float,
+                       measure_transport_freq: int, sweep_batch: int, field_sq: bool) -> None:
+    """The measurement phase (src/Simulation.jl:133-228) of the chains of ctx
+    on the throughput path, up to sweep_batch sweeps per device batch: draw the
+    batch (per sweep and chain standard_complex_normal(rng, (N, 2)), then one
+    rng.random(), always), load_draws, sweep_log with the snapshot cadence
+    measure_transport_freq at the offset that keeps the cadence of the global
+    sweep number, run_sweeps, then the results, the observables records and the
+    snapshots read back: the same observables.csv rows (chain k into outs[k],
+    results[k]) and the snapshots into tqs[k].add(i, Δ).  field_sq: S_d(q),
+    S_s(q) of every sweep into field_sq.npy, (n_measure, 2, Ly, Lx), of each
+    chain's directory."""
+    K, B = len(outs), int(sweep_batch)
+    if B < 1:
+        raise ValueError("sweep_batch must be at least 1 (or None)")
+    freq = max(int(measure_transport_freq), 0)
+    for o in outs:
+        o.tee(f"Sweep batches: up to {B} sweeps per device batch, one Metropolis uniform drawn for every sweep")
+    t1 = time.time()
+    acc_total = np.zeros(K, dtype=np.int64)
+    sq_all = []
+    setting = None
+    done = 0
+    while done < n_measure:
+        b = min(B, n_measure - done)
+        noise = np.empty((b, K, p.N, 2), dtype=np.complex128)
+        u = np.empty((b, K))
+        for s in range(b):
+            for k in range(K):
+                noise[s, k] = H.standard_complex_normal(rngs[k], (p.N, 2))
+                u[s, k] = rngs[k].random()
+        ctx.load_draws(noise, u)
+        # sweep s of the batch is sweep i = done + s + 1 of the run; snapshots where i % freq == 0
+        want = (field_sq, freq, (freq - 1 - done) % freq if freq else 0)
+        if want != setting:
+            ctx.sweep_log(observables=True, field_sq=field_sq, snapshot_every=freq, snapshot_offset=want[2])
+            setting = want
+        ctx.run_sweeps(0, b, Nt, dt, p.mass)
+        acc, dH = ctx.sweep_results(0, b)
+        rec = ctx.sweep_observables(0, b)
+        if field_sq:
+            sq_all.append(ctx.sweep_field_sq(0, b))
+        sweeps, snaps = ctx.sweep_snapshots(0, b) if freq else ((), None)
+        at = {int(s): m for m, s in enumerate(sweeps)}
+        for s in range(b):
+            i = done + s + 1
+            for k in range(K):
+                obs = H.ObservablesResult(*(float(v) for v in rec[s, k, :9]))
+                a, d = bool(acc[s, k]), float(dH[s, k])
+                acc_total[k] += a
+                outs[k].observables(i, a, d, obs)
+                results[k].records.append((i, a, d, obs))
+                if s in at:
+                    tqs[k].add(i, snaps[at[s], k])
+                if i % 10 == 0:
+                    outs[k].tee("Meas %d/%d. Acc=%.2f. E=%.4f" % (i, n_measure, acc_total[k] / i, obs.total_energy))
+        done += b
+    for tq in tqs:
+        tq.flush()
+    ctx.sweep_log(observables=False)
+    for k in range(K):
+        if field_sq:
+            sq = np.concatenate(sq_all)[:, k] if sq_all else np.zeros((0, 2, p.Ly, p.Lx))
+            np.save(os.path.join(outs[k].out_dir, "field_sq.npy"), sq)
+        results[k].meas_acceptance = acc_total[k] / max(n_measure, 1)
+        outs[k].tee(f"Measurement Done. Total Time: {round(time.time() - t1, 2)}s")
+
+
 def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_measure: int = 500,
                    Nt_therm_init: int = 10, Nt_measure: int = 5, measure_transport_freq: int = 1,
                    bin_size: int = 5, verbose: bool = True, rng: np.random.Generator | None = None,
@@ -620,7 +692,8 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
                    spectral_maps: dict | None = None, current_response: dict | None = None,
                    operator_response: dict | None = None,
                    nambu_response: dict | None = None, response_map: dict | None = None,
-                   correlations: dict | None = None, integrator=None) -> SimulationResult:
+                   correlations: dict | None = None, integrator=None, sweep_batch: int | None = None,
+                   field_sq: bool = False) -> SimulationResult:
     """src/Simulation.jl:34-236.  Files in out_dir: simulation.log (appended),
     observables.csv, transport.csv (one row per transport measurement, every
     measure_transport_freq sweeps; <= 0 disables), and spectra_bins/ — the
@@ -638,7 +711,23 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
     the option.  integrator: the trajectories' splitting and the adaptive
     Nt's lower bound (Integrator), a name, a dict or None (the default: the
     reference's leapfrog, the files as without the keyword).  All are checked
-    before any file is opened."""
+    before any file is opened.
+    sweep_batch: None (the default) takes every measurement sweep through the
+    single-sweep entries and writes every file as before.  B >= 1 runs the
+    measurement phase on the throughput path in batches of up to B sweeps
+    (measure_in_batches): observables and Δ snapshots are logged on the device
+    and read back once per batch, the files are the same ones.  The
+    throughput path wants every uniform before its first sweep, so this mode
+    draws, per sweep, standard_complex_normal(rng, (N, 2)) and then one
+    rng.random() always — the reference's "rand() only when ΔH >= 0"
+    (src/HMC.jl:128) cannot be kept.  The Markov chain is then the same for
+    every B and differs from sweep_batch=None only in which uniforms the
+    generator hands out; simulation.log names the mode.  Thermalisation keeps
+    its per-sweep adaptive loop.  field_sq (with sweep_batch only): S_d(q) and
+    S_s(q) of the pairing field after every measurement sweep into
+    field_sq.npy, (n_measure, 2, Ly, Lx)."""
+    if field_sq and sweep_batch is None:
+        raise ValueError("field_sq needs sweep_batch (the structure factors are logged on the throughput path)")
     rng = rng if rng is not None else np.random.default_rng()
     options = parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
                             operator_response=operator_response, nambu_response=nambu_response,
@@ -670,6 +759,18 @@ def run_simulation(p: H.ModelParameters, out_dir: str, *, n_therm: int = 100, n_
         acc_total = 0
         res = SimulationResult(Nt_fin, acc_th, 0.0)
         tq = TransportQueue.with_options(options, cache.require(), p, out, res, bin_size, transport_batch)
+        if sweep_batch is not None:
+            ctx = cache.require()
+            tq.at_device = False
+            ctx.set_state(state.Delta, None)
+            measure_in_batches(ctx, p, [out], [res], [rng], [tq], n_measure=n_measure, Nt=Nt_measure, dt=dt_meas,
+                               measure_transport_freq=measure_transport_freq, sweep_batch=sweep_batch,
+                               field_sq=field_sq)
+            D, P = ctx.get_state()
+            state.Delta, state.pi = D[0], P[0]
+            cache.E_fermion = float(ctx.fermion_energy()[0])
+            cache.pairing = ctx.pairing()[0]
+            return res
         for i in range(1, n_measure + 1):
             acc, dH = H.hmc_sweep(cache, p, state, Nt=Nt_measure, dt=dt_meas, rng=rng)
             acc_total += int(acc)
@@ -695,7 +796,8 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                           spectral_maps: dict | None = None, current_response: dict | None = None,
                           operator_response: dict | None = None,
                           nambu_response: dict | None = None, response_map: dict | None = None,
-                          correlations: dict | None = None, integrator=None) -> list:
+                          correlations: dict | None = None, integrator=None, sweep_batch: int | None = None,
+                          field_sq: bool = False) -> list:
     """len(out_dirs) independent run_simulation's (src/Simulation.jl:34-236),
     chain k writing out_dirs[k] and drawing from rngs[k] in the reference's
     order (initialize_state, then per sweep randn(ComplexF64) and rand() only
@@ -713,8 +815,12 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
     for every chain, so dH differs at ~1e-12 and a Metropolis decision can
     differ).  spectral_maps, current_response, operator_response,
     nambu_response, response_map, correlations, integrator: as
-    run_simulation's, for every chain."""
+    run_simulation's, for every chain.  sweep_batch, field_sq: as
+    run_simulation's (there the draw order of that mode); every chain then
+    runs the Markov chain of its run_simulation with the same sweep_batch."""
     K = len(out_dirs)
+    if field_sq and sweep_batch is None:
+        raise ValueError("field_sq needs sweep_batch (the structure factors are logged on the throughput path)")
     options = parse_options(p, spectral_maps=spectral_maps, current_response=current_response,
                             operator_response=operator_response, nambu_response=nambu_response,
                             response_map=response_map, correlations=correlations)
@@ -755,6 +861,15 @@ def run_simulation_chains(p: H.ModelParameters, out_dirs, rngs, *, n_therm: int 
                 o.tee(f"Settings: Nt={Nt_measure}, dt={round(dt_meas, 5)}")
                 if integ is not None:
                     o.tee(f"Factorisations per trajectory: {integ.stages * Nt_measure}")
+            if sweep_batch is not None:
+                tqs = [TransportQueue.with_options(options, ctx, p, outs[k], results[k], bin_size, transport_batch,
+                                                   chain=k) for k in range(K)]
+                for tq in tqs:
+                    tq.at_device = False
+                measure_in_batches(ctx, p, outs, results, rngs, tqs, n_measure=n_measure, Nt=Nt_measure, dt=dt_meas,
+                                   measure_transport_freq=measure_transport_freq, sweep_batch=sweep_batch,
+                                   field_sq=field_sq)
+                return results
             t1 = time.time()
             acc_total = np.zeros(K, dtype=np.int64)
             tqs = [TransportQueue.with_options(options, ctx, p, outs[k], results[k], bin_size, transport_batch, chain=k)

@@ -222,6 +222,54 @@ int dwh_sweep_results(dwh_ctx* ctx, int64_t first_sweep, int64_t nsweeps, uint8_
                       double* dH);
 int dwh_synchronize(dwh_ctx* ctx);
 
+/* The sweep log: what every sweep of dwh_run_sweeps records on the device for
+ * every chain, by extra launches after the sweep's Metropolis step, so from
+ * the accepted or restored Δ, P, E_f and Tr ρ_hh.  A context that never
+ * enables it makes the launches it made before.  `what` is a mask of
+ *   DWH_LOG_OBS       DWH_OBS_FIELDS doubles: fields 0..8 the reference's
+ *                     ObservablesResult in its order [src/Observables.jl:70-80]
+ *                     (total_energy, Δ_amp, Δ_local, Δ_global, S_Δ, hole_conc,
+ *                     Δ_diff, Δ_pair, Δ_localpair), 9 E_f, 10 Tr ρ_hh,
+ *                     11 Σ|Δ_ij|²;
+ *   DWH_LOG_FIELD_SQ  the pairing field's structure factors: with
+ *                     d_i = (Δ[i,0] - Δ[i,1])/2, s_i = (Δ[i,0] + Δ[i,1])/2,
+ *                     channel 0 = d, 1 = s, site i = x + Lx·y,
+ *                       S_ch(q) = |(1/N) Σ_i f_i exp(-2πi (kx·x/Lx + ky·y/Ly))|²,
+ *                     q = kx + Lx·ky (the momentum indexing and sign of ak0 /
+ *                     akw); S_0(0) is field 4 of the record.  N <= 4096;
+ *   DWH_LOG_SNAPSHOT  Δ after the sweeps sw >= snap_offset with
+ *                     (sw - snap_offset) % snap_every == 0, sw the index into
+ *                     the loaded draws.
+ * dwh_sweep_log settles pending sweeps first, so a batch is never half
+ * logged; what = 0 frees the log.  The buffers are sized for the loaded draws
+ * and zero-filled, by this call and by a dwh_load_draws that grows the draws.
+ * The setting and the buffers survive pole re-selections; after a guard trip
+ * the replayed sweeps are logged again, so the log equals what the
+ * single-sweep path would have produced for every sweep.  DWH_ERR_STATE
+ * between dwh_hmc_trajectory and dwh_hmc_finish; DWH_ERR_ARG, with nothing
+ * changed, for bits outside the mask, for snap_every < 1 or snap_offset < 0
+ * with the snapshot bit, and for N > 4096 with the field bit.
+ * The readers settle like dwh_sweep_results; DWH_ERR_ARG for a range outside
+ * the loaded draws, DWH_ERR_STATE for a part that is not enabled:
+ *   dwh_sweep_observables  obs[f + 12·(c + nchains·k)], sweep first + k;
+ *   dwh_sweep_field_sq     sq[q + N·(ch + 2·(c + nchains·k))];
+ *   dwh_sweep_snapshots    the snapshots of the sweeps in [first, first +
+ *                          nsweeps), ascending: *nsnap their number, sweep[m]
+ *                          their sweeps, Delta per snapshot in dwh_get_state's
+ *                          layout; Delta / sweep NULL: count only.
+ * dwh_sweep_log_layout (host only) is the validation and the sizes those
+ * calls use: counts[0] doubles of obs, counts[1] doubles of sq, counts[2]
+ * snapshots of the range [first, first + nsweeps) of ndraws loaded sweeps. */
+enum { DWH_LOG_OBS = 1, DWH_LOG_FIELD_SQ = 2, DWH_LOG_SNAPSHOT = 4 };
+#define DWH_OBS_FIELDS 12
+int dwh_sweep_log(dwh_ctx* ctx, int32_t what, int64_t snap_every, int64_t snap_offset);
+int dwh_sweep_observables(dwh_ctx* ctx, int64_t first, int64_t nsweeps, double* obs);
+int dwh_sweep_field_sq(dwh_ctx* ctx, int64_t first, int64_t nsweeps, double* sq);
+int dwh_sweep_snapshots(dwh_ctx* ctx, int64_t first, int64_t nsweeps, int64_t* nsnap, int64_t* sweep,
+                        dwh_c128* Delta);
+int dwh_sweep_log_layout(int64_t nchains, int64_t N, int64_t ndraws, int32_t what, int64_t snap_every,
+                         int64_t snap_offset, int64_t first, int64_t nsweeps, int64_t* counts);
+
 /* hipStream_t the context launches on (for events / interop).  The handle
  * stays valid for the context's lifetime, pole re-selections included. */
 int dwh_stream(dwh_ctx* ctx, void** stream);
@@ -232,7 +280,8 @@ int dwh_stream(dwh_ctx* ctx, void** stream);
  * bit 4 "step", bit 5 "gj_edge", bit 6 "cr_gemm", bit 7 "cr_inv", bit 8 "cr_inv_side",
  * bit 9 "eig_own", bit 10 "eig_vendor", bit 11 "cr_sparse", bit 12 "spectral",
  * bit 13 "response", bit 14 "operator", bit 15 "nambu", bit 16 "map",
- * bit 17 "corr_rho", bit 18 "corr_contract", bit 19 "corr_reduce");
+ * bit 17 "corr_rho", bit 18 "corr_contract", bit 19 "corr_reduce",
+ * bit 20 "sweep_log");
  * 0 disables, -1 times everything. */
 int dwh_timing_enable(dwh_ctx* ctx, int32_t enable);
 /* name: "gj_update" (rank-128 paired / rank-64 trailing updates),

@@ -152,6 +152,69 @@ function set_integrator!(cache::GPUCache, kind::Symbol=:omelyan2; λ::Float64=OM
     return nothing
 end
 
+# n sweeps on the throughput path with the device's sweep log (dwh_load_draws,
+# dwh_sweep_log, dwh_run_sweeps and the log's readers, include/dwhmc.h): the
+# draws of all sweeps are taken first — per sweep randn(ComplexF64, N, 2), then
+# one rand(), always, since the device wants every uniform before its first
+# sweep (the reference's "rand() only when ΔH >= 0", src/HMC.jl:128, cannot be
+# kept) — and per sweep the device records the observables (the nine fields of
+# ObservablesResult, then E_f, Tr ρ_hh, Σ|Δ|²), with field_sq the structure
+# factors S_d(q), S_s(q) of the pairing field, and with snap_every > 0 the Δ
+# after the sweeps snap_offset, snap_offset + snap_every, ... (0-based within
+# the call).  Returns (accepted, ΔH, obs 12 x n, sq Lx x Ly x 2 x n or nothing,
+# snapshot sweeps, Δ snapshots N x 2 x m); state.Δ, state.π and the cache end
+# at the last sweep.  Not run, like the rest of this file; the entries are
+# exercised through ctypes by tests/test_sweep_log_gpu.py.
+const DWH_LOG_OBS, DWH_LOG_FIELD_SQ, DWH_LOG_SNAPSHOT = Int32(1), Int32(2), Int32(4)
+const DWH_OBS_FIELDS = 12
+function run_sweeps_logged!(cache::GPUCache, p::ModelParameters, state::SimulationState, n::Int; Nt::Int,
+                            dt::Float64, field_sq::Bool=false, snap_every::Int=0, snap_offset::Int=0)
+    noise = zeros(ComplexF64, p.N, 2, n)
+    uniform = zeros(n)
+    for k in 1:n
+        noise[:, :, k] = randn(ComplexF64, p.N, 2)
+        uniform[k] = rand()
+    end
+    what = DWH_LOG_OBS | (field_sq ? DWH_LOG_FIELD_SQ : Int32(0)) | (snap_every > 0 ? DWH_LOG_SNAPSHOT : Int32(0))
+    accepted, dH = zeros(UInt8, n), zeros(n)
+    obs = zeros(DWH_OBS_FIELDS, n)
+    sq = field_sq ? zeros(p.Lx, p.Ly, 2, n) : nothing
+    nsnap = Ref{Int64}(0)
+    GC.@preserve state noise uniform accepted dH obs begin
+        check(cache.ctx, ccall((:dwh_set_state, libdwhmc), Cint,
+                               (Ptr{Cvoid}, Ptr{ComplexF64}, Ptr{ComplexF64}), cache.ctx, state.Δ, C_NULL))
+        check(cache.ctx, ccall((:dwh_load_draws, libdwhmc), Cint, (Ptr{Cvoid}, Int64, Ptr{ComplexF64}, Ptr{Float64}),
+                               cache.ctx, n, noise, uniform))
+        check(cache.ctx, ccall((:dwh_sweep_log, libdwhmc), Cint, (Ptr{Cvoid}, Int32, Int64, Int64),
+                               cache.ctx, what, snap_every, snap_offset))
+        check(cache.ctx, ccall((:dwh_run_sweeps, libdwhmc), Cint, (Ptr{Cvoid}, Int64, Int64, Int64, Float64, Float64),
+                               cache.ctx, 0, n, Nt, dt, p.mass))
+        check(cache.ctx, ccall((:dwh_sweep_results, libdwhmc), Cint,
+                               (Ptr{Cvoid}, Int64, Int64, Ptr{UInt8}, Ptr{Float64}), cache.ctx, 0, n, accepted, dH))
+        check(cache.ctx, ccall((:dwh_sweep_observables, libdwhmc), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}),
+                               cache.ctx, 0, n, obs))
+        if field_sq
+            GC.@preserve sq check(cache.ctx, ccall((:dwh_sweep_field_sq, libdwhmc), Cint,
+                                                   (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}), cache.ctx, 0, n, sq))
+        end
+    end
+    sweeps, snaps = Int64[], zeros(ComplexF64, p.N, 2, 0)
+    if snap_every > 0
+        check(cache.ctx, ccall((:dwh_sweep_snapshots, libdwhmc), Cint,
+                               (Ptr{Cvoid}, Int64, Int64, Ref{Int64}, Ptr{Int64}, Ptr{ComplexF64}),
+                               cache.ctx, 0, n, nsnap, C_NULL, C_NULL))
+        sweeps, snaps = zeros(Int64, nsnap[]), zeros(ComplexF64, p.N, 2, nsnap[])
+        GC.@preserve sweeps snaps check(cache.ctx, ccall((:dwh_sweep_snapshots, libdwhmc), Cint,
+                                                         (Ptr{Cvoid}, Int64, Int64, Ref{Int64}, Ptr{Int64},
+                                                          Ptr{ComplexF64}), cache.ctx, 0, n, nsnap, sweeps, snaps))
+    end
+    GC.@preserve state check(cache.ctx, ccall((:dwh_get_state, libdwhmc), Cint,
+                                              (Ptr{Cvoid}, Ptr{ComplexF64}, Ptr{ComplexF64}), cache.ctx, state.Δ,
+                                              state.π))
+    n > 0 && (cache.E_fermion = obs[10, n])
+    return accepted .!= 0, dH, obs, sq, sweeps, snaps
+end
+
 # src/Observables.jl:88-222 from what the factorisation caches instead of the
 # eigenpairs: E_f (dwh_fermion_energy, = -Σ_{E>0}(βE + 2 log1pexp(-βE)) of
 # :147-156), P_ij (dwh_pairing, the ρ sums of :172-198) and Tr ρ_hh

@@ -30,6 +30,9 @@ def main():
                     help="measure transport every k sweeps (0: never) -> transport.csv")
     ap.add_argument("--integrator", choices=["leapfrog", "omelyan2"], default=None,
                     help="the trajectories' splitting (default: the context's leapfrog); --Nt stays steps")
+    ap.add_argument("--sweep-batch", type=int, default=None,
+                    help="run the sweeps on the throughput path, up to this many per device batch, with the "
+                         "records logged on the device (default: one call per sweep)")
     ap.add_argument("--out", default="runs/replicas")
     a = ap.parse_args()
 
@@ -57,7 +60,7 @@ def main():
 
     p = m.ModelParameters(a.L, a.L, 1.0, -0.35, -1.08, 1.0, 0.05, a.beta, 0.8, 1.0)
     cfg = rep.ReplicaConfig(chains=a.chains, n_sweeps=a.sweeps, Nt=a.Nt, seed=a.seed,
-                            transport_freq=a.transport_freq,
+                            transport_freq=a.transport_freq, sweep_batch=a.sweep_batch,
                             integrator=None if a.integrator is None else dict(kind=a.integrator))
 
     def make_context(disorder):
