@@ -10,6 +10,8 @@ O_A(i) = Σ_t a_{i,t} Ψ†_{r(i,t)} Ψ_{c(i,t)}, by the definition:
     G_AB(i,j) = Σ_{t,u} a_{i,t} conj(b_{j,u}) conj(ρ[r_A, r_B]) (δ[c_A, c_B] - ρ[c_A, c_B])
     corr[r]   = (1/N) Σ_j G(j ⊕ r, j),    local[q][r] = G(ref_q ⊕ r, ref_q)
 
+`mean_s` / `gmat_s` / `response_s` return (value, S) in the working dtype, S the error
+scale built from S_ρ = |U| diag(f) |U|^T; `mean` / `gmat` / `response` are their values.
 `g_loops` is the explicit loop over terms; `gmat` is the same sum taken a site i
 at a time over all terms of B at once (the tests check one against the other).
 """
@@ -41,14 +43,13 @@ class CorrRef(NRef):
     """mean, G, corr and local of one eigensystem (E ascending, U columns)."""
 
     def rho(self):
-        return (self.U * self.f[None, :]) @ self.U.conj().T
+        """ρ = U diag(f) U^H (formed once)"""
+        if "rho" not in self._x:
+            self._x["rho"] = (self.U * self.f[None, :]) @ self.U.conj().T
+        return self._x["rho"]
 
     def mean(self, fam):
-        rho, ct = self.rho(), R._c(self.dt)
-        out = np.zeros(self.p.N, dtype=ct)
-        for i, (r, c, v) in enumerate(site_terms(fam, self.p.N)):
-            out[i] = np.sum(v.astype(ct) * rho[c, r]) if len(r) else 0
-        return out
+        return self.mean_s(fam)[0]
 
     def g_loops(self, fa, fb):
         """G_AB(i, j) (N, N) by the explicit loop over the terms"""
@@ -64,39 +65,76 @@ class CorrRef(NRef):
                 G[i, j] = acc
         return G
 
-    def gmat(self, fa, fb):
+    def srho(self):
+        """S_ρ = |U| diag(f) |U|^T, the error scale of ρ's entries"""
+        if "srho" not in self._x:
+            A = np.abs(self.U)
+            self._x["srho"] = (A * self.f[None, :]) @ A.T
+        return self._x["srho"]
+
+    def mean_s(self, fam):
+        """(m_A(i), S(i)) in the working dtype, S = Σ_t |a_{i,t}| S_ρ[c, r]"""
+        rho, sr, ct = self.rho(), self.srho(), R._c(self.dt)
+        out, S = np.zeros(self.p.N, dtype=ct), np.zeros(self.p.N, dtype=self.dt)
+        for i, (r, c, v) in enumerate(site_terms(fam, self.p.N)):
+            if len(r):
+                out[i], S[i] = np.sum(v.astype(ct) * rho[c, r]), np.sum(np.abs(v).astype(self.dt) * sr[c, r])
+        return out, S
+
+    def gmat_s(self, fa, fb, scale=True):
+        """(G, S) (N, N) in the working dtype;
+        S(i, j) = Σ_{t,u} |a| |b| S_ρ[r_A, r_B] (δ[c_A, c_B] + S_ρ[c_A, c_B]): δ + S_ρ, not
+        |δ - ρ| (what of δ - ρ lies below eps is not resolved by ρ)"""
         N, rho, ct = self.p.N, self.rho(), R._c(self.dt)
+        sr = self.srho() if scale else None
         A = site_terms(fa, N)
         order = np.argsort(np.asarray(fb.site), kind="stable")
         sb = np.asarray(fb.site)[order]
         rb, cb = np.asarray(fb.row)[order], np.asarray(fb.col)[order]
         vb = np.conj(np.asarray(fb.val)[order].astype(ct))
         G = np.zeros((N, N), dtype=ct)
+        S = np.zeros((N, N), dtype=self.dt) if scale else None
         if len(sb) == 0:
-            return G
+            return G, S
         for i, (ra, ca, a) in enumerate(A):
             if len(ra) == 0:
                 continue
-            X = np.conj(rho[ra[:, None], rb[None, :]]) * ((ca[:, None] == cb[None, :]) - rho[ca[:, None], cb[None, :]])
+            eq = ca[:, None] == cb[None, :]
+            X = np.conj(rho[ra[:, None], rb[None, :]]) * (eq - rho[ca[:, None], cb[None, :]])
             w = (a.astype(ct)[:, None] * X).sum(axis=0) * vb
             np.add.at(G[i], sb, w)
-        return G
+            if scale:
+                Y = sr[ra[:, None], rb[None, :]] * (eq + sr[ca[:, None], cb[None, :]])
+                np.add.at(S[i], sb, (np.abs(a).astype(self.dt)[:, None] * Y).sum(axis=0) * np.abs(vb))
+        return G, S
 
-    def response(self, fams, pairs, ref_sites=()):
-        """(corr (npairs, Ly, Lx), local (npairs, nref, Ly, Lx), mean (nfam, Ly, Lx)) in complex128"""
+    def gmat(self, fa, fb):
+        return self.gmat_s(fa, fb, scale=False)[0]
+
+    def response_s(self, fams, pairs, ref_sites=(), scale=True):
+        """dict corr (npairs, N), local (npairs, nref, N), mean (nfam, N): each (value, S) in the
+        working dtype; corr's S is (1/N) Σ_j of G's, local's is G's at the reference site
+        (scale=False: every S is None)"""
         p = self.p
         T = translate_table(p.Lx, p.Ly)
         j = np.arange(p.N)
         corr, local = [], []
         for a, b in pairs:
-            G = self.gmat(fams[a], fams[b])
-            corr.append(G[T, j[None, :]].sum(axis=1) / p.N)
-            local.append([G[T[:, q], q] for q in ref_sites])
-        shp = (p.Ly, p.Lx)
-        mean = np.stack([self.mean(f) for f in fams]).astype(np.complex128).reshape((len(fams),) + shp)
-        corr = np.asarray(corr).astype(np.complex128).reshape((len(pairs),) + shp)
-        local = np.asarray(local).astype(np.complex128).reshape((len(pairs), len(ref_sites)) + shp)
-        return corr, local, mean
+            G, S = self.gmat_s(fams[a], fams[b], scale)
+            corr.append([M[T, j[None, :]].sum(axis=1) / p.N for M in (G, S) if M is not None])
+            local.append([[M[T[:, q], q] for q in ref_sites] for M in (G, S) if M is not None])
+        mean = [self.mean_s(f)[:2 if scale else 1] for f in fams]
+
+        def both(parts, shape):
+            out = [np.asarray([x[k] for x in parts]).reshape(shape) for k in range(2 if scale else 1)]
+            return tuple(out) if scale else (out[0], None)
+        return dict(corr=both(corr, (len(pairs), p.N)), local=both(local, (len(pairs), len(ref_sites), p.N)),
+                    mean=both(mean, (len(fams), p.N)))
+
+    def response(self, fams, pairs, ref_sites=()):
+        """(corr (npairs, Ly, Lx), local (npairs, nref, Ly, Lx), mean (nfam, Ly, Lx)) in complex128"""
+        r, shp = self.response_s(fams, pairs, ref_sites, scale=False), (self.p.Ly, self.p.Lx)
+        return tuple(r[k][0].astype(np.complex128).reshape(r[k][0].shape[:-1] + shp) for k in ("corr", "local", "mean"))
 
 
 class OracleCorrelations(OracleContext):

@@ -1,7 +1,7 @@
 """Prescribed eigensystems for the tests of the measurement reductions
 (tests/test_measure_reference.py on the CPU, tests/test_measure_reductions.py
-on the device): spectrum families that put levels on either side of every
-branch rule on purpose, each with its condition checked by `check_family`, and
+and tests/test_measure_reductions_pairs.py on the device): spectrum families
+that put levels on either side of every branch rule on purpose, each with its condition checked by `check_family`, and
 the lattices whose 2N is chosen against the 256-pair tile.  U is the Q of a
 seeded complex Gaussian matrix (measure_reference.haar) unless the family
 says otherwise: nothing needs U to diagonalise anything.

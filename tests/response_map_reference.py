@@ -10,7 +10,9 @@ With X = U^H W U, ΔE_nm = E_m - E_n, Ω_l = 2π l/β, by the definition:
     retarded ω:   w = (f_n - f_m)/(ΔE - ω - iη), 0 where |f_n - f_m| < 1e-12
 
 f_n - f_m and the branch decisions are measure_reference's (cancellation-free,
-taken on the fp64 input).  Whole matrices are formed: the tests sample them.
+taken on the fp64 input).  `dmat` / `rho` / `response` form whole matrices and the
+tests sample them; `sampled` / `rho_s` evaluate only the pattern entries and return
+(value, S), S = Σ |term| of the value's sum, in the working dtype.
 """
 import numpy as np
 
@@ -48,11 +50,34 @@ class MapRef(NRef):
     def rho(self):
         return (self.U * self.f[None, :]) @ self.U.conj().T
 
+    def sampled(self, W, pattern, nl, omega=(), eta=None):
+        """(D, S) (nz, npat) in the working dtype, only at the pattern's entries and
+        without forming D(z): D_e = (U[a_e, :] K_z) · conj(U[b_e, :]), one row product
+        per distinct a; S_e = Σ_nm |U[a_e, n]| |w_nm(z)| |X_nm| |U[b_e, m]|"""
+        X, U = self.x(W), self.U
+        pat = np.asarray(pattern)
+        rows, inv = np.unique(pat[:, 0], return_inverse=True)
+        Ua, Ub = U[rows], np.conj(U[pat[:, 1]])
+        aUa, aUb, aX = np.abs(Ua), np.abs(Ub), np.abs(X)
+        nz = nl + len(omega)
+        D, S = np.empty((nz, len(pat)), dtype=R._c(self.dt)), np.empty((nz, len(pat)), dtype=self.dt)
+        for z in range(nz):
+            w = self.weight(z, nl, omega, eta)
+            D[z] = np.sum((Ua @ (w * X))[inv] * Ub, axis=1)
+            S[z] = np.sum((aUa @ (np.abs(w) * aX))[inv] * aUb, axis=1)
+        return D, S
+
+    def rho_s(self, pattern):
+        """(ρ[a_e, b_e], S_ρ[a_e, b_e]) in the working dtype, S_ρ = |U| diag(f) |U|^T"""
+        pat = np.asarray(pattern)
+        Ua, Ub = self.U[pat[:, 0]], self.U[pat[:, 1]]
+        return np.sum(Ua * self.f[None, :] * np.conj(Ub), axis=1), np.sum(np.abs(Ua) * self.f[None, :] * np.abs(Ub), axis=1)
+
     def response(self, Ws, pattern, nl, omega=(), eta=None):
         """(dmap (nops, nz, npat), rho (npat,)) in complex128 on the pattern"""
         a, b = np.asarray(pattern)[:, 0], np.asarray(pattern)[:, 1]
         dmap = np.stack([self.dmat(W, nl, omega, eta)[:, a, b] for W in Ws]) if nl + len(omega) > 0 else None
-        return (None if dmap is None else dmap.astype(np.complex128)), self.rho()[a, b].astype(np.complex128)
+        return (None if dmap is None else dmap.astype(np.complex128)), self.rho_s(pattern)[0].astype(np.complex128)
 
 
 class OracleMap(OracleContext):

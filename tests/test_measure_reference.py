@@ -16,14 +16,24 @@ tests/test_measure_reductions.py holds the device to.
     against the eigenvectors of a real H_BdG, and the ambiguity allowance:
     on every case of the device file the pairs within a factor 2 of the Δf
     rule may move σ(ω) / χ''(ω) by less than a tenth of the bound without them.
+  * the (value, S) references of the Nambu response, the response maps and the
+    correlations (tests/measure_pair_cases.py): the fp64 run is the restatement
+    the parity tests use, S >= |value|, the sampled map is the whole matrix,
+    g_loops is the vectorised G, every injected spectrum meets its family and
+    keeps out of the Δf window, and the yardstick stays within 2N eps S on
+    every device case.
 """
 import mpmath as mp
 import numpy as np
 import pytest
 
 import measure_cases as MC
+import measure_pair_cases as MP
 import measure_reference as R
+from correlation_reference import CorrRef
+from nambu_reference import NRef
 from oracle_measurements import CurrentRef as RefCurrent, OperatorRef as RefOperator
+from response_map_reference import MapRef
 from test_current_response import QLIST, _case
 
 LD, F8 = np.longdouble, np.float64
@@ -243,3 +253,155 @@ def test_ambiguity_allowance_is_small(oracle, family, beta, n2):
     _, (c2, S2), amb = R.operator_response(E, U, p, beta, V, -1, 1, eta, w, LD, br)
     _, (y2, _), _ = R.operator_response(E, U, p, beta, V, -1, 1, eta, w, F8, br)
     assert np.all(amb <= R.bound(c2, y2, S2, n2) / 10)
+
+
+# --------------------------------------------------------------------------- the pair, map and correlation references
+# (tests/measure_pair_cases.py, held on the device by tests/test_measure_reductions_pairs.py)
+EPS = float(np.finfo(F8).eps)
+
+
+@pytest.fixture(scope="module")
+def VX(dwhmc):
+    return dwhmc.vertices
+
+
+def _parts(v):
+    v = np.asarray(v)
+    return (v.real, v.imag) if np.iscomplexobj(v) else (v,)
+
+
+def _scale_covers(v, S, what):
+    """S = Σ |term| >= |value| (a rounding of the sums apart)"""
+    v, S = np.abs(np.asarray(v)).astype(LD), np.asarray(S, dtype=LD)
+    assert v.shape == S.shape, (what, v.shape, S.shape)
+    assert np.all(v <= S * (1 + LD(1e-12))), (what, float(np.max(v - S)))
+
+
+@pytest.mark.parametrize("n2", [32, 70])
+def test_value_and_scale_runs_are_the_restatements(oracle, VX, n2):
+    """The fp64 (value, S) runs against NRef.response, MapRef.response (whole matrices) and
+    CorrRef.response: the same bits where the code is shared, within 4 eps S where the map
+    is summed in another order; and S >= |value| in both dtypes."""
+    beta = 8.0
+    p = MC.params(oracle, n2, beta)
+    E, U, br = MP.system("generic", n2, beta)
+    vs = MP.nambu_vertices(VX, p)
+    Ws, pairs, w = [v.dense(p.N) for v in vs], MP.nambu_pairs(7, 5), R.grid(*MP.grid(9))
+    pat = np.concatenate([MP.pattern(VX, p, k) for k in ("bond", "random", "col70")])
+    fams = [VX.local_family(k, p) for k in MP.CORR_KINDS] + [MP.hand_family(VX, p.N)]
+    sites = [0, p.N - 1]
+    for dt in (F8, LD):
+        nr = NRef(p, E, U, beta=beta, dt=dt, br=br)
+        (chi, Sc), (c2, S2) = nr.response_s(Ws, pairs, 3, w, MP.ETA)
+        _scale_covers(chi, Sc, "chi")
+        _scale_covers(c2, S2, "chi2")
+        mr = MapRef(p, E, U, beta=beta, dt=dt, br=br)
+        D, SD = mr.sampled(Ws[0], pat, 3, MP.OMEGAS[4], MP.ETA)
+        rho, Sr = mr.rho_s(pat)
+        _scale_covers(D, SD, "dmap")
+        _scale_covers(rho, Sr, "rho")
+        cr = CorrRef(p, E, U, beta=beta, dt=dt, br=br)
+        cs = cr.response_s(fams, MP.CORR_PAIRS, sites)
+        for k, (v, S) in cs.items():
+            _scale_covers(v, S, k)
+        if dt is LD:
+            continue
+        old_chi, old_c2 = nr.response(Ws, pairs, 3, w, MP.ETA)
+        assert np.array_equal(old_chi, chi) and np.array_equal(old_c2, c2)
+        old_d, old_rho = mr.response(Ws[:1], pat, 3, MP.OMEGAS[4], MP.ETA)
+        assert np.array_equal(old_rho, rho)
+        for a, b in zip(_parts(D), _parts(old_d[0])):
+            print("map, sampled against whole, worst / (eps S)", float(np.max(np.abs(a - b) / (EPS * SD))))
+            assert np.all(np.abs(a - b) <= 4 * EPS * SD)
+        old = cr.response(fams, MP.CORR_PAIRS, sites)
+        for k, o in zip(("corr", "local", "mean"), old):
+            assert np.array_equal(o.reshape(cs[k][0].shape), cs[k][0]), k
+
+
+def test_sampled_map_is_the_whole_matrix(oracle, VX):
+    """2N = 32, long double: the pattern entries of U (w ∘ X) U^H formed whole against the
+    row products.  Both sum the same 2N x 2N terms of absolute sum S in another order:
+    each within 2N eps S of the exact sum."""
+    n2, beta = 32, 8.0
+    p = MC.params(oracle, n2, beta)
+    for family in ("generic", "twins", "dfedge"):
+        E, U, br = MP.system(family, n2, beta)
+        mr = MapRef(p, E, U, beta=beta, dt=LD, br=br)
+        W = MP.map_vertices(VX, p)[0].dense(p.N)
+        pat = np.stack(np.meshgrid(np.arange(n2), np.arange(n2), indexing="ij"), -1).reshape(-1, 2)
+        D, S = mr.sampled(W, pat, 3, MP.OMEGAS[4], MP.ETA)
+        whole = mr.dmat(W, 3, MP.OMEGAS[4], MP.ETA).reshape(D.shape)
+        assert np.abs(whole).max() > 1e-3
+        for a, b in zip(_parts(D), _parts(whole)):
+            assert np.all(np.abs(a - b) <= 2 * n2 * EPS_LD * S), family
+        rho, Sr = mr.rho_s(pat)
+        assert np.all(np.abs(rho - mr.rho().reshape(-1)) <= 2 * n2 * EPS_LD * Sr)
+
+
+@pytest.mark.parametrize("dt", [F8, LD], ids=["yardstick", "reference"])
+def test_g_loops_is_the_vectorised_g(oracle, VX, dt):
+    """4 x 4: the explicit loop over the terms against gmat_s.  Two orders of one sum of
+    t_A t_B products of absolute sum <= S: apart by at most t_A t_B eps S."""
+    n2, beta = 32, 8.0
+    p = MC.params(oracle, n2, beta)
+    E, U, br = MP.system("zeros", n2, beta)
+    cr = CorrRef(p, E, U, beta=beta, dt=dt, br=br)
+    fams = [VX.local_family("current_x", p), MP.hand_family(VX, p.N)]
+    eps = EPS_LD if dt is LD else EPS
+    for a, b in ((0, 0), (1, 1), (0, 1), (1, 0)):
+        G, S = cr.gmat_s(fams[a], fams[b])
+        L = cr.g_loops(fams[a], fams[b])
+        ta, tb = (np.bincount(np.asarray(fams[k].site), minlength=p.N) for k in (a, b))
+        terms = np.maximum(1, ta[:, None] * tb[None, :])
+        assert np.abs(G).max() > 1e-3 and np.all(G[ta == 0] == 0) and np.all(G[:, tb == 0] == 0)
+        for x, y in zip(_parts(G), _parts(L)):
+            assert np.all(np.abs(x - y) <= terms * eps * S), (a, b)
+
+
+def test_device_spectra_meet_their_families():
+    """every spectrum a device case injects: its family's condition, and no pair within a
+    factor 2 of the Δf rule, so the ambiguity allowance of those cases is 0"""
+    for family, beta, n2 in MP.spectra():
+        E, U, br = MP.system(family, n2, beta)
+        MC.check_family(family, E, beta)
+        assert not br.ambiguous_df().any(), (family, beta, n2)
+        assert np.abs(U.conj().T @ U - np.eye(n2)).max() <= 1e-12
+    fams = {f for f, _, _ in MP.spectra()}
+    assert {"generic", "twins", "dfedge", "cold15", "cold25", "zeros", "ph"} <= fams
+
+
+def _yardstick_within_floor(ref, yard, n2, what):
+    """|yardstick - reference| <= 2N eps S on every value (so S >= |value| too): the bar of
+    such a case is its floor, and only the device can miss it"""
+    for k in ref:
+        if ref[k] is None or ref[k][0] is None:
+            continue
+        (v, S), (y, _) = ref[k], yard[k]
+        _scale_covers(v, S, (what, k))
+        floor = LD(n2) * LD(EPS) * np.asarray(S, dtype=LD)
+        worst = 0.0
+        for a, b in zip(_parts(np.asarray(y).astype(R._c(LD)) if np.iscomplexobj(y) else y), _parts(v)):
+            err = np.abs(np.asarray(a, dtype=LD) - b)
+            assert np.all(err <= R.bound(b, a, S, n2)), (what, k)
+            ok = floor > 0
+            worst = max(worst, float(np.max(err[ok] / floor[ok])) if ok.any() else 0.0)
+            assert np.all(err <= floor), (what, k, worst)
+        print(f"YARDSTICK {what} {k}: {worst:.3g} of the floor")
+
+
+@pytest.mark.parametrize("case", MP.NAMBU, ids=lambda c: "-".join(str(x) for x in c))
+def test_yardstick_nambu(oracle, VX, case):
+    *_, ref, yard = MP.nambu_case(oracle, VX, *case)
+    _yardstick_within_floor(ref, yard, case[2], "nambu")
+
+
+@pytest.mark.parametrize("case", MP.MAP, ids=lambda c: "-".join(str(x) for x in c))
+def test_yardstick_map(oracle, VX, case):
+    *_, ref, yard = MP.map_case(oracle, VX, *case)
+    _yardstick_within_floor(ref, yard, case[2], "map")
+
+
+@pytest.mark.parametrize("case", MP.CORR, ids=lambda c: "-".join(str(x) for x in c))
+def test_yardstick_corr(oracle, VX, case):
+    *_, ref, yard = MP.corr_case(oracle, VX, *case)
+    _yardstick_within_floor(ref, yard, case[2], "corr")
