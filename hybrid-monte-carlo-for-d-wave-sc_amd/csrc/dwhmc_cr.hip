@@ -1018,22 +1018,27 @@ __device__ __forceinline__ int64_t cr_slot_off(int v) {
 }
 
 // Epilogue of both descriptor forms: out = [C] + sg (t1 - t2, t3 - t1 - t2)
-// at O (the lane's first output element; C likewise, cpf its values loaded at
-// tile start).  KSPLIT > 1: the waves of a tile sum their partials through LDS
+// at base + so + vo (the lane's first output element: the batch item's pool
+// base, the wave-uniform and the per-lane part of its offset, the form the
+// write-through store takes, st16_through; C likewise, cpf its values loaded
+// at tile start).  KSPLIT > 1: the waves of a tile sum their partials through LDS
 // (every wave of the workgroup reaches the barrier, valid or not).
 template <int BP, int MI, int KSPLIT, int ST = kStorePlain>
 __device__ __forceinline__ void cr_tile_store(d4 (&t1)[MI][MI], d4 (&t2)[MI][MI], d4 (&t3)[MI][MI], double sg,
-                                              double2* O, bool hasc, const double2 (&cpf)[MI * MI * 4 / KSPLIT],
-                                              bool valid, [[maybe_unused]] bool stamp = false) {
+                                              double2* base, uint32_t so, uint32_t vo, bool hasc,
+                                              const double2 (&cpf)[MI * MI * 4 / KSPLIT], bool valid,
+                                              [[maybe_unused]] bool stamp = false) {
   constexpr int NV = MI * MI * 4;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, kq = w % KSPLIT;
+  [[maybe_unused]] double2* O = base + so + vo;
   auto put = [&](int v, double2 x) {
     if (hasc) {
       const double2 c = cpf[v / KSPLIT];
       x.x += c.x;
       x.y += c.y;
     }
-    st16<ST>(O + cr_slot_off<BP, MI>(v), x);
+    if constexpr (ST == kStoreThrough) st16_through(base, so, vo + (uint32_t)cr_slot_off<BP, MI>(v), x);
+    else st16<ST>(O + cr_slot_off<BP, MI>(v), x);
   };
   // complex partial of register slot v
   auto partial = [&](int v) {
@@ -1128,7 +1133,8 @@ __device__ __forceinline__ void cr_gemm_wg(double2* __restrict__ pool, int64_t i
       t2[mi][ni] = d4{0.0, 0.0, 0.0, 0.0};
       t3[mi][ni] = d4{0.0, 0.0, 0.0, 0.0};
     }
-  double2* O = base + out * BB + (int64_t)(tr * TS + lk) * BP + tc * TS + lr;
+  // the output tile's origin within the item (uniform: gt is) and the lane's element in it
+  const uint32_t oso = (uint32_t)(out * BB + (int64_t)(tr * TS) * BP + tc * TS), ovo = (uint32_t)(lk * BP + lr);
   const bool hasc = cin >= 0;
   double2 cpf[NV / KSPLIT];
 #pragma unroll
@@ -1144,7 +1150,7 @@ __device__ __forceinline__ void cr_gemm_wg(double2* __restrict__ pool, int64_t i
       if (kq == 1) run(std::integral_constant<int, 1>{});
     }
   }
-  cr_tile_store<BP, MI, KSPLIT, ST>(t1, t2, t3, sg, O, hasc, cpf, valid);
+  cr_tile_store<BP, MI, KSPLIT, ST>(t1, t2, t3, sg, base, oso, ovo, hasc, cpf, valid);
 }
 
 // Argument order: what the first loads need leads (the build preloads the
@@ -1227,9 +1233,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGemmWaves)
     }
   }
 #ifdef CR_GEMM_STAMPS
-  cr_tile_store<BP, 1, KSPLIT, ST>(t1, t2, t3, sg, base + out + lo, hasc, cpf, valid, g_gemm_on);
+  cr_tile_store<BP, 1, KSPLIT, ST>(t1, t2, t3, sg, base, out, (uint32_t)lo, hasc, cpf, valid, g_gemm_on);
 #else
-  cr_tile_store<BP, 1, KSPLIT, ST>(t1, t2, t3, sg, base + out + lo, hasc, cpf, valid);
+  cr_tile_store<BP, 1, KSPLIT, ST>(t1, t2, t3, sg, base, out, (uint32_t)lo, hasc, cpf, valid);
 #endif
 #ifdef CR_GEMM_STAMPS
   if (g_gemm_on) __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");

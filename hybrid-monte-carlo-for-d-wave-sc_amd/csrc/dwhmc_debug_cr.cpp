@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <set>
 #include <string>
@@ -214,6 +215,11 @@ int dwh_debug_cr_launch(int32_t device, int32_t kind, int32_t BP, int32_t nblk, 
   if (e == hipSuccess && prod) e = sc.up(&dtasks, tk.data(), tk.size());
   if (e == hipSuccess && !slots.empty()) e = sc.up(&dslots, slots.data(), slots.size());
   if (e != hipSuccess) return fail(nullptr, DWH_ERR_HIP, std::string("cr test buffers: ") + hipGetErrorString(e));
+  // DWHMC_DEBUG_CR_STORE=1: the product tiles of a K-split 16 x 16 launch and
+  // the side products are written through, as the plan has them on the step
+  // path (the default here: plain everywhere)
+  const char* se = std::getenv("DWHMC_DEBUG_CR_STORE");
+  const int through = se && *se == '1' ? kStoreThrough : kStorePlain;
   switch (kind) {
     case DWH_CR_INV:
       launch_cr_inv(c, dpool, dblk, ddst, dslot, ninv, dld, nullptr);
@@ -225,10 +231,12 @@ int dwh_debug_cr_launch(int32_t device, int32_t kind, int32_t BP, int32_t nblk, 
       launch_cr_inv0(c, dpool, dblk, drblk, ddst, dslot, ninv, dld, dldA, nullptr);
       break;
     case DWH_CR_GEMM:
-      launch_cr_gemm(c, dpool, dtasks, ntasks, maxt32, maxt16, dslots, nswg, cfg, sg, nullptr);
+      launch_cr_gemm(c, dpool, dtasks, ntasks, maxt32, maxt16, dslots, nswg, cfg, sg, nullptr,
+                     ts == 16 && ksplit > 1 ? through : kStorePlain);
       break;
     default:
-      launch_cr_inv_side(c, dpool, dblk, ddst, dslot, ninv, dld, dtasks, ntasks, maxt32, nullptr);
+      launch_cr_inv_side(c, dpool, dblk, ddst, dslot, ninv, dld, dtasks, ntasks, maxt32, nullptr, SiteGuard{},
+                         kStorePlain, through);
       break;
   }
   e = hipGetLastError();

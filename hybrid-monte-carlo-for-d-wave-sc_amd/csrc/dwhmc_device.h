@@ -102,8 +102,11 @@ __device__ __forceinline__ double2 cinv_fast(double2 a) {
 //   plain    global_store_dwordx4: the line stays dirty in this XCD's L2 and
 //            is written back at the end of the launch (the release every
 //            dependent launch ends with);
-//   through  two relaxed agent-scope 8-byte stores (global_store_dwordx2 sc1):
-//            written through while the kernel runs, the L2 drops the line;
+//   through  written through while the kernel runs, the L2 drops the line: one
+//            16-byte buffer store with sc1 where the site has a wave-uniform
+//            base (st16_through below: every site the plan writes through);
+//            this pointer form issues two relaxed agent-scope 8-byte stores
+//            (global_store_dwordx2 sc1);
 //   stream   non-temporal (global_store_dwordx4 nt): the line is marked for
 //            early eviction but stays in the L2.
 template <int POL>
@@ -119,6 +122,37 @@ __device__ __forceinline__ void st16(double2* p, double2 v) {
     static_assert(POL == 0, "store policy: 0 plain, 1 write-through, 2 non-temporal");
     *p = v;
   }
+}
+
+// The (base, offset) form of the write-through store, used where the plan
+// picks write-through (the K-split product epilogues and the side products):
+// ONE 16-byte buffer store with sc1 (buffer_store_dwordx4 ... sc1), which
+// costs the writer what a plain store does and leaves a same-XCD reader most
+// of its L2 hits (tools/micro/boundary_dirty.hip, THROUGH16).  base: the batch
+// item's first pool element, wave-uniform (the resource descriptor lives in
+// SGPRs); soff / voff: the uniform and the per-lane part of the element
+// offset within the item, whose byte offsets fit 32 bits (plan_cr refuses a
+// lattice whose batch item reaches 2^32 bytes; none dwh_create takes does).
+// In the built code the descriptor and soff are SGPRs at every site
+// (buffer_store_dwordx4 v[..], v, s[..:..], s.. offen sc1, no waterfall loop):
+// the bases come from a scalar slot load (k_cr_gemm16) or a readfirstlane'd
+// tile index (cr_gemm_wg).  The pointer form above keeps the two
+// halves: the sites that use it have no uniform base, and the plan stores
+// plain there.  -DDWH_ST16_THROUGH_HALVES: the two halves here too (A/B
+// libraries only).
+__device__ __forceinline__ void st16_through(double2* base, uint32_t soff, uint32_t voff, double2 v) {
+#ifdef DWH_ST16_THROUGH_HALVES
+  st16<1>(base + soff + voff, v);
+#else
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  // raw buffer over the item: stride 0, no record limit (the plan bounds the
+  // offsets), descriptor word 3 = DATA_FORMAT 32-bit (bits 15-18 = 4; an
+  // untyped store ignores the format); cache policy bit 4 of the builtin's aux
+  // operand = sc1 (bit 0 sc0, bit 1 nt)
+  constexpr int kRsrcNoLimit = -1, kRsrcWord3Raw32 = 0x00020000, kAuxSc1 = 16;
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, kRsrcNoLimit, kRsrcWord3Raw32);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)(voff * 16u), (int)(soff * 16u), kAuxSc1);
+#endif
 }
 
 // Bijective XCD-aware remap of a 1D grid (cdna_hip_programming.md §5): blocks

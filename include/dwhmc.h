@@ -811,7 +811,10 @@ int dwh_debug_level0(dwh_ctx* ctx, int64_t chain, int64_t pole, int32_t refill, 
  * HP x BP, nt in 1..4, ts 32 only where HP % 32 == 0, ksplit 4 only with ts 16,
  * no task writing a block the launch reads or another task writes, no
  * inversion writing another's source: DWH_ERR_ARG with the reason in
- * dwh_last_error(NULL), and no launch. */
+ * dwh_last_error(NULL), and no launch.  Stores are plain; with
+ * DWHMC_DEBUG_CR_STORE=1 (read at every call) the tiles of a 16 x 16 launch
+ * with a K split and the side products are written through, as the plan
+ * stores them on the step path. */
 enum { DWH_CR_INV = 0, DWH_CR_INV0 = 1, DWH_CR_GEMM = 2, DWH_CR_INV_SIDE = 3 };
 int dwh_debug_cr_launch(int32_t device, int32_t kind, int32_t BP, int32_t nblk, int32_t nbatch, int32_t nslots,
                         dwh_c128* pool, double* ldpart, int32_t ninv, const int32_t* blk, const int32_t* rblk,
